@@ -13,9 +13,19 @@ inside north_star's 1e-3 relative fp32 tolerance (round-5 verdict, item 1b; DESI
 (`--dtype f16` / `bf16`) and exact f32 are labelled legs.  N > 1 shards by batch (weak scaling): one process per GPU, two RCCL
 gradient all-reduces per step; `python bench.py --gpus N` without a launcher re-executes itself under torch.distributed.run.
 
-Rank 0 prints ONE LEAN JSON line on stdout (lean_line(): 3 KB, hard limit 6 KB -- the driver keeps the last 8 KB of stdout, and
-round 5's 25 KB line did not parse there) and writes the FULL object to bench_detail.json (gpurun_out/ when that directory exists,
-else next to this file; --detail PATH).  The lean line carries the contract keys, the dominant kernel's `roofline` (with `traffic`),
+A plain run measures the headline only: it sets up, warms up, times --steps steps, writes --dump-outputs if given and prints the
+result line (the contract keys, `config`, `timed_region_s`).  --full adds everything else below -- the sustained leg, the all-reduce
+cost, the rooflines (instrumented iterations of their own), the other compute modes, cfg5, inference, the data pipeline, the CPU
+baseline -- and bench_detail.json; the --no-* switches leave single legs out of a --full run.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as float32 DIR/<name>.npy: the four losses it returned
+(loss_real, loss_fake, adv_loss, content_loss) and the weights its two AdamW updates left (generator.npy, discriminator.npy: every
+floating-point state_dict tensor, flattened, in state_dict order; 22 MB for cfg3).  Weights, inputs and label noise are seeded, so
+runs with the same arguments compute from the same numbers.
+
+Rank 0 prints ONE LEAN JSON line on stdout (lean_line(): 3 KB, hard limit 6 KB -- a consumer may keep only the last 8 KB of stdout,
+and round 5's 25 KB line did not parse there); with --full it also writes the FULL object to bench_detail.json (--detail PATH; the
+default is given in --help).  The --full line carries the contract keys, the dominant kernel's `roofline` (with `traffic`),
 `cpu_baseline`, and one scalar per leg.
 
 Keys of the full object (bench_detail.json; DESIGN.md section 4 describes each):
@@ -40,6 +50,7 @@ Keys of the full object (bench_detail.json; DESIGN.md section 4 describes each):
                 pipeline in fp16 (host bytes -> H2D -> G -> uint8 epilogue -> D2H): median of three warm passes.
 """
 import argparse
+import contextlib
 import hashlib
 import importlib
 import json
@@ -283,10 +294,11 @@ def time_steps(step_fn, lr, hr, steps, warmup, world, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step_fn(lr, hr)
+        last = step_fn(lr, hr)
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    time_steps.last = last              # what the final timed step returned (--dump-outputs)
     per_rank = [elapsed]
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -411,8 +423,9 @@ def lean_line(full):
     prec = cfg.pop("precision", None)
     line["config"] = {k: (clip(v, 140) if isinstance(v, str) else v) for k, v in cfg.items()}
     roof = full.get("roofline") or {}
-    line["roofline"] = {k: roof[k] for k in _ROOFLINE_KEYS if k in roof}
-    line["roofline"].setdefault("traffic", None)
+    if roof:            # (a plain run measures no roofline)
+        line["roofline"] = {k: roof[k] for k in _ROOFLINE_KEYS if k in roof}
+        line["roofline"].setdefault("traffic", None)
     fam = roof.get("family") or {}
     if fam:
         line["roofline"]["family_frac"] = fam.get("frac")
@@ -467,6 +480,23 @@ def lean_line(full):
     return text
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, losses, trainer):
+    """--dump-outputs: the losses the last timed step returned and the Generator / Discriminator weights it left, as float32
+    <directory>/<name>.npy (the module docstring lists the files)."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in losses.items()}
+    for name, net in (("generator", trainer.generator), ("discriminator", trainer.discriminator)):
+        arrays[name] = torch.cat([v.detach().float().reshape(-1) for v in net.state_dict().values() if v.is_floating_point()]).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "bench: the outputs are %d bytes" % total
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -490,7 +520,16 @@ def main():
     ap.add_argument("--detail", default=None, help="where the FULL object goes (default: gpurun_out/bench_detail.json when gpurun_out/ exists, else ./bench_detail.json)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 5 s sustained legs that follow a short timed region")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replays")
+    ap.add_argument("--full", action="store_true", help="every leg besides the headline (sustained, all-reduce cost, rooflines, the other compute "
+                                                        "modes, cfg5, inference, data pipeline, CPU baseline) and bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses and the G / D weights it left to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:       # a plain run measures the headline only
+        args.no_sustained = args.no_cfg5 = args.no_cpu_baseline = args.no_inference = True
+        args.no_f32 = args.no_x3 = args.no_f16 = args.no_bf16 = True
 
     # FSR_BENCH_FORCE_SPAWN=1 takes the launcher path for N = 1 as well (tests: the self-spawn logic on a one-GPU box)
     if (args.gpus > 1 or os.environ.get("FSR_BENCH_FORCE_SPAWN") == "1") and "WORLD_SIZE" not in os.environ:
@@ -524,11 +563,13 @@ def main():
     hr = torch.rand(B, 3, hr_size, hr_size, device=device) * 2 - 1
 
     step_fn, launch = build_step(pkg, trainer, lr, hr, not args.no_graph)
-    with ClockSampler(local_rank) as clk:
+    with (ClockSampler(local_rank) if args.full else contextlib.nullcontext()) as clk:
         elapsed = time_steps(step_fn, lr, hr, args.steps, args.warmup, world, device)
     per_rank = list(time_steps.per_rank)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:     # before anything else steps the trainer
+        dump_outputs(args.dump_outputs, time_steps.last, trainer)
 
     def sustained_leg(fn, ms_guess, nominal_batch):
         """>= --sustained-seconds of back-to-back steps with the shader clock sampled: what the rate settles at."""
@@ -545,7 +586,7 @@ def main():
     # N > 1 (or a 1-rank RCCL world): what the two gradient exchanges cost a step, outside the timed region -- HIP events from
     # the moment the main stream hands a gradient arena to RCCL to the moment it may continue (distributed.GradSync.record)
     allreduce = None
-    if dist_mod.is_distributed():
+    if dist_mod.is_distributed() and args.full:
         dist_mod.GradSync.record = []
         n_ar = 10
         for _ in range(n_ar):
@@ -566,8 +607,6 @@ def main():
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             allreduce["ms_in_allreduce_max_over_ranks"] = round(float(t.item()), 4)
 
-    roofline, executed_gflop_per_image = measure_roofline(trainer, ops, lr, hr, args.dtype, ms_per_step, B)
-
     out = {"metric": wl["metric"],
            "value": round(value, 3), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -579,17 +618,19 @@ def main():
                       "launch": launch,
                       "precision": PRECISION_NOTE[args.dtype]},
            "timed_region_s": round(elapsed, 3),
-           "ms_per_step_ranks": {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3)},
-           "clock": clk.summary(),
-           "step_gflop_executed_per_image": round(executed_gflop_per_image, 2),
-           "step_tflops_executed": round(value * executed_gflop_per_image / 1e3, 2),
-           "step_gflop_reference_graph_per_image": wl["gflop_ref"],
-           "roofline": roofline}
+           "ms_per_step_ranks": {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3)}}
+    if args.full:
+        roofline, executed_gflop_per_image = measure_roofline(trainer, ops, lr, hr, args.dtype, ms_per_step, B)
+        out.update({"clock": clk.summary(),
+                    "step_gflop_executed_per_image": round(executed_gflop_per_image, 2),
+                    "step_tflops_executed": round(value * executed_gflop_per_image / 1e3, 2),
+                    "step_gflop_reference_graph_per_image": wl["gflop_ref"],
+                    "roofline": roofline})
 
     # `peak` is the dense MFMA figure at the 2.4 GHz boost clock; under a dense kernel the part runs power-limited well
     # below it (sysfs pp_dpm_sclk sampled over the timed region), and with memory traffic lower still
     # (profiles/r03_wgrad_ablation.txt).  Reported beside `frac`, never instead of it.
-    sclk = (out["clock"] or {}).get("sclk_mhz_mean")
+    sclk = (out.get("clock") or {}).get("sclk_mhz_mean")
     if sclk:
         pk = roofline["peak"] * sclk / NOMINAL_SCLK_MHZ
         roofline["at_measured_clock"] = {"sclk_mhz_mean": sclk, "nominal_sclk_mhz": NOMINAL_SCLK_MHZ, "peak": round(pk, 1),
@@ -625,7 +666,7 @@ def main():
             out[dt + "_mode"] = precision_leg(dt, MODE_DESCRIBED[dt], MODE_MEETS[dt])
             if abs(out[dt + "_mode"]["roofline"]["peak"] - MFMA_PEAK_TFLOPS["x3"]) < 1e-6:
                 out[dt + "_mode"]["roofline"]["peak_note"] = "2500 / 3 TFLOP/s: three bf16 MFMAs per algorithmic multiply-add"
-    if abs(roofline["peak"] - MFMA_PEAK_TFLOPS["x3"]) < 1e-6:
+    if args.full and abs(roofline["peak"] - MFMA_PEAK_TFLOPS["x3"]) < 1e-6:
         roofline["peak_note"] = "2500 / 3 TFLOP/s: three bf16 MFMAs per algorithmic multiply-add"
 
     if rank == 0 and world == 1 and not args.no_cfg5:
@@ -810,7 +851,7 @@ def main():
         out["cpu_baseline"] = cpu_baseline()
     if world > 1:
         torch.distributed.barrier()
-    if rank == 0:
+    if rank == 0 and args.full:
         detail = args.detail or os.path.join(ROOT, "gpurun_out" if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else "", "bench_detail.json")
         try:
             with open(detail, "w") as f:
@@ -818,6 +859,7 @@ def main():
             out["detail_file"] = os.path.relpath(detail, ROOT)
         except OSError as exc:
             print("bench: could not write %s (%s)" % (detail, exc), file=sys.stderr)
+    if rank == 0:
         print(lean_line(out), flush=True)
     if dist_mod.is_distributed():
         torch.distributed.destroy_process_group()

@@ -121,7 +121,7 @@ def test_bench_self_spawns_ranks_and_runs_the_rccl_path():
     env = dict(os.environ, FSR_BENCH_FORCE_SPAWN="1", FSR_FORCE_DIST="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--full",
                         "--no-cpu-baseline", "--no-inference", "--no-f32", "--no-x3", "--no-bf16", "--no-sustained"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -129,6 +129,31 @@ def test_bench_self_spawns_ranks_and_runs_the_rccl_path():
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["unit"] == "images/s" and d["value"] > 0
     assert d["config"]["collectives"] == "rccl world 1" and d["config"]["launch"].startswith("3 phase hipGraphs")
     assert d["roofline"]["bound"] == "mfma" and 0 < d["roofline"]["frac"] < 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py` without --full: the headline mode's contract keys and nothing that takes runs of its own (no roofline, no
+    other legs, no bench_detail.json); --dump-outputs writes the last timed step's four losses and the weights it left, float32."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--dump-outputs", str(out), "--detail", str(tmp_path / "detail.json")], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "x3v" and d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert d["value"] > 0 and abs(d["ms_per_step"] - 2 * 1e3 / d["value"]) < 1e-2 * d["ms_per_step"]
+    assert "roofline" not in d and "cpu_baseline" not in d and set(d["legs_images_per_s"]) == {"x3v"}
+    assert not (tmp_path / "detail.json").exists()
+    names = sorted(p.name for p in out.iterdir())
+    assert names == sorted(["loss_real.npy", "loss_fake.npy", "adv_loss.npy", "content_loss.npy", "generator.npy", "discriminator.npy"])
+    for n in names:
+        a = np.load(out / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+    assert np.load(out / "generator.npy").size == 925646 and np.load(out / "discriminator.npy").size == 4684033
 
 
 def test_native_png_ingest_matches_pil(tmp_path):

@@ -11,20 +11,20 @@ TAG=${2:-r06}
 SMODES=${3:-"x3v x3 f16 bf16 f32"}
 PMODES=${3:-"x3v x3 f16"}
 O=$R/gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
-COMMON="--steps 5 --warmup 2 --no-cpu-baseline --no-inference --no-graph --no-f32 --no-x3 --no-f16 --no-bf16 --no-sustained --no-cfg5"
+COMMON="--full --steps 5 --warmup 2 --no-cpu-baseline --no-inference --no-graph --no-f32 --no-x3 --no-f16 --no-bf16 --no-sustained --no-cfg5"
 cd /tmp
 if [ "$WHAT" = stats ] || [ "$WHAT" = all ]; then
   for M in $SMODES; do
     FSR_SIDE_STREAM=0 FSR_WGRAD_STREAM=0 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$M -o bench -- python $R/bench.py --dtype $M $COMMON --detail $O/bench_detail_$M.json > $O/rocprof_$M.log 2>&1
     cp $O/prof_$M/bench_kernel_stats.csv $O/bench_kernel_stats_$M.csv; rm -f $O/prof_$M/bench_kernel_trace.csv
   done
-  FSR_SIDE_STREAM=0 FSR_WGRAD_STREAM=0 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_cfg5 -o bench -- python $R/bench.py --workload cfg5 --steps 5 --warmup 2 --no-graph --no-sustained --detail $O/bench_detail_cfg5.json > $O/rocprof_cfg5.log 2>&1
+  FSR_SIDE_STREAM=0 FSR_WGRAD_STREAM=0 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_cfg5 -o bench -- python $R/bench.py --full --workload cfg5 --steps 5 --warmup 2 --no-graph --no-sustained --detail $O/bench_detail_cfg5.json > $O/rocprof_cfg5.log 2>&1
   cp $O/prof_cfg5/bench_kernel_stats.csv $O/bench_kernel_stats_cfg5.csv; rm -f $O/prof_cfg5/bench_kernel_trace.csv
 fi
 if [ "$WHAT" = pmc ] || [ "$WHAT" = all ]; then
   for M in $PMODES; do
     for C in FETCH_SIZE WRITE_SIZE; do
-      FSR_SIDE_STREAM=0 FSR_WGRAD_STREAM=0 timeout 500 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/pmc_${M}_$C -o step -- python $R/bench.py --dtype $M --steps 1 --warmup 1 --no-cpu-baseline --no-inference --no-graph --no-f32 --no-x3 --no-f16 --no-bf16 --no-sustained --no-cfg5 --detail $O/pmc_detail_${M}.json > $O/pmc_${M}_$C.log 2>&1
+      FSR_SIDE_STREAM=0 FSR_WGRAD_STREAM=0 timeout 500 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/pmc_${M}_$C -o step -- python $R/bench.py --full --dtype $M --steps 1 --warmup 1 --no-cpu-baseline --no-inference --no-graph --no-f32 --no-x3 --no-f16 --no-bf16 --no-sustained --no-cfg5 --detail $O/pmc_detail_${M}.json > $O/pmc_${M}_$C.log 2>&1
     done
     L=$(python -c "import sys,json; print(json.load(open('$O/pmc_detail_${M}.json'))['roofline']['family']['launches_per_step'])")
     OUT=$R/profiles/conv_traffic.json; [ $M != f16 ] && OUT=$R/profiles/conv_traffic_$M.json

@@ -6,7 +6,7 @@ O=gpurun_out; mkdir -p $O
 ( time timeout 1500 python -m pytest tests -m gpu -x -q --durations=12 ) > $O/r6_tests.log 2>&1
 cp $O/parity_errors.log $O/r6_parity_errors.log 2>/dev/null
 bash tools/gpu_artifacts.sh pmc r06 "x3v" > $O/r6_artifacts_pmc.log 2>&1
-( time python bench.py --steps 20 --warmup 5 ) > $O/r6_bench.log 2> $O/r6_bench.err
+( time python bench.py --full --steps 20 --warmup 5 ) > $O/r6_bench.log 2> $O/r6_bench.err
 cp $O/bench_detail.json $O/r6_bench_detail.json 2>/dev/null
 bash tools/gpu_artifacts.sh stats r06 "x3v" > $O/r6_artifacts_stats.log 2>&1
 rm -rf $O/r06/prof_*/ $O/r06/pmc_*_SIZE 2>/dev/null

@@ -1,5 +1,5 @@
 """HBM traffic of the 3x3 conv forward / data-gradient kernels per iteration from two rocprofv3 --pmc passes
-(FETCH_SIZE, WRITE_SIZE; counter_collection.csv) over `bench.py --steps 1 --warmup 1 --no-graph --no-f32` (= 4 iterations).
+(FETCH_SIZE, WRITE_SIZE; counter_collection.csv) over `bench.py --full --steps 1 --warmup 1 --no-graph --no-f32` (= 4 iterations).
 FETCH_SIZE on gfx950 counts half the bytes (MI355X_MICROARCH.md): x2.  Units: KB.
 
     python tools/pmc_traffic.py FETCH.csv WRITE.csv ITERS LAUNCHES_PER_ITER [OUT.json]

@@ -15,7 +15,7 @@ done
 unset FSR_C64V3 FSR_C64T3
 for V in v2 v3; do
   if [ $V = v2 ]; then export FSR_C64V3=0; else unset FSR_C64V3; fi
-  python bench.py --dtype f16 --steps 20 --warmup 5 --no-cpu-baseline --no-cfg5 --no-f32 --no-x3 --no-bf16 --no-sustained --inference-dtypes f16,bf16 --inference-seconds 3 --detail $O/r6_inf_$V.json 2>/dev/null | tail -1 > $O/r6_inf_$V.log
+  python bench.py --full --dtype f16 --steps 20 --warmup 5 --no-cpu-baseline --no-cfg5 --no-f32 --no-x3 --no-bf16 --no-sustained --inference-dtypes f16,bf16 --inference-seconds 3 --detail $O/r6_inf_$V.json 2>/dev/null | tail -1 > $O/r6_inf_$V.log
 done
 unset FSR_C64V3
 python tools/cpu_threads.py 4,8,12,16,24 > $O/r6_cpu_threads_fine.txt 2>&1
