@@ -16,9 +16,11 @@ FSR_F32, FSR_BF16, FSR_F16, FSR_X3 = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU, ACT_TANH = 0, 1, 2, 3, 4
 CONV_FWD, CONV_DGRAD = 0, 1
 PACK_FWD, PACK_FWD_PS, PACK_DGRAD, PACK_DGRAD_PS = 0, 1, 2, 3
-OUT_DTYPE, OUT_F32, OUT_U8 = 0, 1, 2
+OUT_DTYPE, OUT_F32, OUT_U8, OUT_I420 = 0, 1, 2, 3
+YUV_BT601, YUV_BT709 = 0, 1                 # fsr_conv_desc.yuv_matrix, fsr_i420_to_image
+SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_image's input
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
@@ -31,6 +33,7 @@ class ConvDesc(ctypes.Structure):
         ("oh", c_int), ("ow", c_int), ("cout", c_int),
         ("stride", c_int), ("act", c_int), ("slope", c_float),
         ("pixel_shuffle", c_int), ("in_pixel_shuffled", c_int), ("out_f32", c_int), ("pool2", c_int), ("mask_is_addend", c_int), ("pack_lin", c_int),
+        ("yuv_matrix", c_int), ("yuv_full_range", c_int),
     ]
 
 
@@ -70,6 +73,7 @@ SIGNATURES = {
     "fsr_image_to_nhwc": (c_int, [c_int, P, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_float, c_float, c_float,
                                   c_float, c_float, c_float, P, c_int, P]),
     "fsr_u8_to_image": (c_int, [P, P, c_ll, P]),
+    "fsr_i420_to_image": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_pack_conv3x3_c3": (c_int, [c_int, P, c_int, P, c_int, P]),
     "fsr_tanh_bwd_image": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, c_int, P, P, P, P]),
     "fsr_conv3x3_c3_fwd": (c_int, [c_int, P, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_float, c_float, c_float, c_float,

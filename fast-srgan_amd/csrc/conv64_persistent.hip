@@ -9,7 +9,7 @@
 // 72 KB, so a persistent workgroup keeps it next to its halos and walks tiles:
 //   conv64_v2_kernel       64-channel output blocks, stride 1: XOR-swizzled 128-byte rows, halo by LDS-DMA into two
 //                          buffers, one barrier per tile, epilogue deferred into the next tile
-//   conv64_thin_kernel     the 64 -> 3 ends (float / uint8 output): 9 x 16 filter rows, two workgroups per CU
+//   conv64_thin_kernel     the 64 -> 3 ends (float / uint8 / I420 output): 9 x 16 filter rows, two workgroups per CU
 //   conv64_s2fwd_kernel    64 -> 64 stride-2 forward, streaming (3.1d)
 //   conv64_s2dgrad_kernel  64 -> 64 stride-2 data gradient, all four parity classes per tile (3.1c)
 // Same operand mapping, tap table and epilogue semantics (bias, ReLU / LeakyReLU / identity, InstanceNorm statistics, fused
@@ -205,19 +205,44 @@ __global__ __launch_bounds__(NTHR64, 2) void conv64_thin_kernel(const ConvKArgs 
       const int ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
       const int gx = tx * 16 + l15, gyb = ty * 16 + wave * 2;
       const bool col_ok = gx < a.GW;
-      // float output, Cout <= 16 valid channels (lane group lg holds channels 4 lg .. 4 lg + 3): scale, bias, tanh / slope
+      if (a.out_f32 == FSR_OUT_I420) {
+        // I420 planes of the RGB head (Cout = 3, tanh, even FOH / FOW: host checked).  The wave's rows gyb, gyb + 1 (gyb even) and
+        // the columns of lanes l15, l15 ^ 1 are one 2x2 chroma block: every lane takes part in the shuffle, lane group 0 (channels
+        // 0 .. 2) stores -- two Y samples per lane, the block's Cb / Cr from the even column.  Partial tiles: an even GW / GH keeps
+        // both columns / rows of a block on the same side of the border.
+        float t[2][3];
 #pragma unroll
-      for (int m = 0; m < 2; ++m) {
-        if (col_ok && gyb + m < a.GH) {
-          const size_t off = (((size_t)img * a.FOH + gyb + m) * a.FOW + gx) * a.Cout + lg * 4;
+        for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (lg * 4 + r < a.Cout) {
-              float v = acc[m][0][r] * oscale[r] + bias[0][r];
-              v = (a.act == FSR_ACT_TANH) ? tanhf(v) : (v > 0.f ? v : v * slope);
-              if (a.out_f32 == FSR_OUT_U8) ((unsigned char*)a.out)[off + r] = image_u8(v);   // HWC uint8 image (inference)
-              else ((float*)a.out)[off + r] = v;
-            }
+          for (int r = 0; r < 3; ++r) t[m][r] = tanhf(acc[m][0][r] * oscale[r] + bias[0][r]);
+        unsigned char yv[2], cb, cr;
+        i420_quad(t, a.yuv_matrix, a.yuv_full, yv, cb, cr);
+        if (lg == 0 && col_ok && gyb < a.GH) {
+          const size_t plane = (size_t)a.FOH * a.FOW, cplane = plane >> 2;
+          unsigned char* o = (unsigned char*)a.out + (size_t)img * (plane + 2 * cplane);
+          o[(size_t)gyb * a.FOW + gx] = yv[0];
+          o[(size_t)(gyb + 1) * a.FOW + gx] = yv[1];
+          if (!(l15 & 1)) {
+            const size_t c = (size_t)(gyb >> 1) * (a.FOW >> 1) + (gx >> 1);
+            o[plane + c] = cb;
+            o[plane + cplane + c] = cr;
+          }
+        }
+      } else {
+        // float output, Cout <= 16 valid channels (lane group lg holds channels 4 lg .. 4 lg + 3): scale, bias, tanh / slope
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+          if (col_ok && gyb + m < a.GH) {
+            const size_t off = (((size_t)img * a.FOH + gyb + m) * a.FOW + gx) * a.Cout + lg * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (lg * 4 + r < a.Cout) {
+                float v = acc[m][0][r] * oscale[r] + bias[0][r];
+                v = (a.act == FSR_ACT_TANH) ? tanhf(v) : (v > 0.f ? v : v * slope);
+                if (a.out_f32 == FSR_OUT_U8) ((unsigned char*)a.out)[off + r] = image_u8(v);   // HWC uint8 image (inference)
+                else ((float*)a.out)[off + r] = v;
+              }
+          }
         }
       }
     }
@@ -821,7 +846,8 @@ int fsr_conv64_persistent_try(int dtype, ConvKArgs& a, int S, hipStream_t stream
   // x3 (a.Cin = 128 physical bf16 channels): the thin kernel only (the head and the image gradients; round 6)
   const bool x3 = dtype == FSR_X3;
   if ((dtype != FSR_BF16 && dtype != FSR_F16 && !x3) || S != 1 || a.Cin != (x3 ? 128 : 64) || a.ntaps != 9) return 0;
-  // thin: float output of at most 16 channels (head conv, image gradients); otherwise 64-channel blocks
+  // thin: float output of at most 16 channels (head conv, image gradients); otherwise 64-channel blocks.  Its geometry -- 16 x 16
+  // tiles, wave w holding rows 2w and 2w + 1 -- keeps every 2x2 block of an I420 output (FSR_OUT_I420) inside one wave.
   const bool thin = a.CoutPad == 16 && a.out_f32 && !a.ps && !a.in_ps && !a.stats && !a.preact && !a.dmask && !a.pool2;
   if (x3 && (!thin || a.Cout > 8 || a.wlin)) return 0;      // (eight filter rows per tap in LDS: conv64_thin_kernel<bf16_t, true>)
   if (!thin) {

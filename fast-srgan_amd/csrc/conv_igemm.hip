@@ -64,7 +64,7 @@ __device__ __forceinline__ unsigned tap_code(const ConvKArgs& a, int t) {
 // by a wave-uniform branch, replace one path with per-element flag tests:
 //   plain : T output, every channel valid (Cout % 16 == 0), optional pre-activation copy   (all big layers)
 //   ps    : as plain, stored depth-to-space (PixelShuffle(2) fused, model.py:36)
-//   thin  : float output with fewer than 16 channels per tile (head conv + tanh, image gradients)
+//   thin  : float output with fewer than 16 channels per tile (head conv + tanh, image gradients), uint8 / I420 head images
 // ReLU / LeakyReLU / PReLU / identity are ONE formula: v > 0 ? v : v * slope with slope 0 / s / a / 1.
 template <typename T>
 __device__ __forceinline__ void store_vec4(T* p, f32x4 v) {
@@ -515,6 +515,40 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvK
   const bool col_ok = gx < a.GW;
   if (BN == 16 && ((a.out_f32 && sizeof(T) == 2) || a.Cout % 16 != 0 || a.out_f32 == FSR_OUT_U8)) {  // only the 16-wide configs carry this code
     // ---- thin / float path (memory-bound layers): per-element guards, optional scale, tanh
+    if constexpr (MT % 2 == 0 && NT == 1 && S == 1) {   // (launch_cfg refuses FSR_OUT_I420 for every other configuration)
+      if (a.out_f32 == FSR_OUT_I420) {
+        // I420 planes of the RGB head (Cout = 3, tanh, forward, even FOH / FOW: host checked): rows gyb + 2 k, gyb + 2 k + 1 of the
+        // wave (gy0 = ty * TH and gyb are even) and the columns of lanes l15, l15 ^ 1 are one 2x2 chroma block.  Every lane shuffles,
+        // lane group 0 (channels 0 .. 2) stores; an even GW / GH keeps a block on one side of a partial tile's border.
+        const size_t plane = (size_t)a.FOH * a.FOW, cplane = plane >> 2;
+        unsigned char* o = (unsigned char*)a.out + (size_t)img * (plane + 2 * cplane);
+        static_for<0, MT / 2>([&](auto kc) {
+          constexpr int k = decltype(kc)::value;
+          float t[2][3];
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+              float v = acc[2 * k + m][0][r];
+              if (a.bias) v += a.bias[cob + r < a.Cout ? cob + r : 0];
+              t[m][r] = tanhf(v);
+            }
+          unsigned char yv[2], cb, cr;
+          i420_quad(t, a.yuv_matrix, a.yuv_full, yv, cb, cr);
+          const int gy = gyb + 2 * k;
+          if (lg == 0 && col_ok && gy < a.GH) {
+            o[(size_t)gy * a.FOW + gx] = yv[0];
+            o[(size_t)(gy + 1) * a.FOW + gx] = yv[1];
+            if (!(l15 & 1)) {
+              const size_t c = (size_t)(gy >> 1) * (a.FOW >> 1) + (gx >> 1);
+              o[plane + c] = cb;
+              o[plane + cplane + c] = cr;
+            }
+          }
+        });
+        return;
+      }
+    }
     static_for<0, NT>([&](auto nc) {
       constexpr int n = decltype(nc)::value;
       const int co = cob + n * 16;
@@ -698,6 +732,13 @@ static int launch_cfg(ConvKArgs& a, hipStream_t stream, ConvKArgs* more = nullpt
   if (a.in_ps && (a.Cin / 4) % KC != 0)
     return fsr_fail(-2, "conv3x3: pixel-shuffled input needs (Cin/4)=%d to be a multiple of the chunk %d", a.Cin / 4, KC);
   if (a.CoutPad % BN != 0) return fsr_fail(-2, "conv3x3: padded Cout=%d is not a multiple of %d", a.CoutPad, BN);
+  // FSR_OUT_I420 is stored by the thin epilogue of the stride-1 configurations, whose waves must hold whole 2x2 blocks: an even
+  // number of rows per wave (rows gy0 + wm * MT + m with an even tile height) and one 16-column tile per wave (lanes l15, l15 ^ 1
+  // are neighbouring columns).  Of the configurations that serve a thin (CoutPad = 16) head only <8, 16, 4, 1> exists: MT = 2.
+  if (a.out_f32 == FSR_OUT_I420 && (S != 1 || BN != 16 || TH % 2 != 0 || (TH / WM) % 2 != 0 || BN / 16 / WN != 1 || nmore > 0 ||
+                                    a.osy != 1 || a.osx != 1 || a.ooy != 0 || a.oox != 0))
+    return fsr_fail(-2, "conv3x3: I420 output: configuration <TH=%d, BN=%d, WM=%d, WN=%d, S=%d> would split a 2x2 block between waves",
+                    TH, BN, WM, WN, S);
   a.nblk_n = a.CoutPad / BN;
   a.premask = (stage_mode() & 65536) ? 0 : 1;
   a.HH = (TH - 1) * S + 3;

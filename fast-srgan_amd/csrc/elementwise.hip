@@ -415,6 +415,45 @@ __global__ __launch_bounds__(256) void u8_to_image_kernel(const unsigned char* _
     dst[i] = (float)src[i] / 127.5f - 1.0f;
 }
 
+// I420 frames -> float [n,h,w,3] = 2 c - 1 of the decoded RGB c in [0, 1] (fsr_i420_to_image; the colour contract is DESIGN.md
+// "Video"): one thread per pixel, chroma upsampled bilinearly with edge clamp at the declared siting -- luma pixel (y, x) reads
+// chroma at ((y - 1/2) / 2, (x - 1/2) / 2) (C420jpeg) or ((y - 1/2) / 2, x / 2) (C420mpeg2); then the inverse of the encode
+// matrix, R, G, B clamped to [0, 1] (no 8-bit RGB in between).
+__global__ __launch_bounds__(256) void i420_to_image_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, int n, int h,
+                                                            int w, int mpeg2, int matrix, int full) {
+  const int ch = (h + 1) >> 1, cw = (w + 1) >> 1;
+  const long long plane = (long long)h * w, cplane = (long long)ch * cw, fbytes = plane + 2 * cplane;
+  const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
+  const float kg = 1.f - kr - kb;
+  const float ys = full ? 255.f : 219.f, yo = full ? 0.f : 16.f, cs = full ? 255.f : 224.f;
+  const long long total = (long long)n * plane;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    const long long img = i / plane;
+    const int p = (int)(i - img * plane), y = p / w, x = p - y * w;
+    const unsigned char* f = src + img * fbytes;
+    const float cy = 0.5f * (float)y - 0.25f, cx = mpeg2 ? 0.5f * (float)x : 0.5f * (float)x - 0.25f;
+    const float fy0 = floorf(cy), fx0 = floorf(cx);
+    const float fy = cy - fy0, fx = cx - fx0;
+    const int iy = (int)fy0, ix = (int)fx0;      // >= -1
+    const int y0 = iy < 0 ? 0 : iy, y1 = iy + 1 < ch ? iy + 1 : ch - 1, x0 = ix < 0 ? 0 : ix, x1 = ix + 1 < cw ? ix + 1 : cw - 1;
+    float c[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const unsigned char* q = f + plane + k * cplane;
+      const float top = (1.f - fx) * (float)q[y0 * cw + x0] + fx * (float)q[y0 * cw + x1];
+      const float bot = (1.f - fx) * (float)q[y1 * cw + x0] + fx * (float)q[y1 * cw + x1];
+      c[k] = (1.f - fy) * top + fy * bot;
+    }
+    const float ey = ((float)f[p] - yo) / ys, ecb = (c[0] - 128.f) / cs, ecr = (c[1] - 128.f) / cs;
+    const float r = ey + 2.f * (1.f - kr) * ecr, b = ey + 2.f * (1.f - kb) * ecb;
+    const float g = (ey - kr * r - kb * b) / kg;
+    float* o = dst + i * 3;
+    o[0] = 2.f * fminf(fmaxf(r, 0.f), 1.f) - 1.f;
+    o[1] = 2.f * fminf(fmaxf(g, 0.f), 1.f) - 1.f;
+    o[2] = 2.f * fminf(fmaxf(b, 0.f), 1.f) - 1.f;
+  }
+}
+
 // ------------------------------------------------------------------ out = a + b (gradient accumulation of a tensor with two consumers)
 template <typename T>
 __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long long units) {
@@ -745,6 +784,20 @@ extern "C" int fsr_u8_to_image(const uint8_t* frames, float* img, long long coun
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(u8_to_image_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, frames, img, count);
   return fsr_check_launch("u8_to_image_kernel");
+}
+
+extern "C" int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
+                                 fsr_stream_t stream_) {
+  if (!frames || !img || n <= 0 || h <= 0 || w <= 0) return fsr_fail(-1, "fsr_i420_to_image: bad argument");
+  if ((siting != FSR_SITING_JPEG && siting != FSR_SITING_MPEG2) || (matrix != FSR_YUV_BT601 && matrix != FSR_YUV_BT709) ||
+      (full_range != 0 && full_range != 1))
+    return fsr_fail(-2, "fsr_i420_to_image: unknown siting %d / matrix %d / range %d", siting, matrix, full_range);
+  if ((long long)h * w >= (1LL << 31)) return fsr_fail(-2, "fsr_i420_to_image: frames of 2^31 or more pixels are not supported");
+  long long blocks = ((long long)n * h * w + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(i420_to_image_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, frames, img, n, h, w,
+                     siting == FSR_SITING_MPEG2 ? 1 : 0, matrix, full_range);
+  return fsr_check_launch("i420_to_image_kernel");
 }
 
 extern "C" size_t fsr_tanh_bwd_scratch(void) { return (size_t)512 * 64 * 3 * sizeof(float); }

@@ -147,9 +147,22 @@ static int conv3x3_impl(const fsr_conv_desc* d, const void* in, const void* pack
                    dact_mask || oscale || (d->oh & 1) || (d->ow & 1) || d->cout % 16 != 0 || d->act == FSR_ACT_TANH))
     return fsr_fail(-2, "fsr_conv3x3: pool2 is for stride-1 forward launches of the 16-bit modes with even output extents "
                         "(no statistics / pre-activation / mask / scale tensors, no pixel shuffle)");
-  if (d->out_f32 < 0 || d->out_f32 > FSR_OUT_U8) return fsr_fail(-2, "fsr_conv3x3: unknown output kind %d", d->out_f32);
+  if (d->out_f32 < 0 || d->out_f32 > FSR_OUT_I420) return fsr_fail(-2, "fsr_conv3x3: unknown output kind %d", d->out_f32);
   if (d->out_f32 == FSR_OUT_U8 && (d->act != FSR_ACT_TANH || d->cout > 16 || d->pixel_shuffle || d->mode != FSR_CONV_FWD))
     return fsr_fail(-2, "fsr_conv3x3: uint8 image output is for tanh heads (forward, cout <= 16)");
+  if (d->out_f32 == FSR_OUT_I420) {
+    // the conditions of FSR_OUT_U8, three (RGB) channels, whole 2x2 chroma blocks, and none of the optional tensors the thin
+    // epilogues would otherwise read or write per channel
+    if (d->act != FSR_ACT_TANH || d->cout != 3 || d->pixel_shuffle || d->mode != FSR_CONV_FWD || d->stride != 1 || stats || preact ||
+        dact_mask || oscale)
+      return fsr_fail(-2, "fsr_conv3x3: I420 output is for 3-channel tanh heads (forward, stride 1, no pixel shuffle, no statistics / "
+                          "pre-activation / mask / scale tensors)");
+    if ((d->oh & 1) || (d->ow & 1)) return fsr_fail(-2, "fsr_conv3x3: I420 output needs even output extents (%d x %d)", d->oh, d->ow);
+    if ((d->yuv_matrix != FSR_YUV_BT601 && d->yuv_matrix != FSR_YUV_BT709) || (d->yuv_full_range != 0 && d->yuv_full_range != 1))
+      return fsr_fail(-2, "fsr_conv3x3: I420 output: unknown colour matrix %d / range %d", d->yuv_matrix, d->yuv_full_range);
+  }
+  a.yuv_matrix = d->yuv_matrix;
+  a.yuv_full = d->yuv_full_range;
   if (a.ps && stats) return fsr_fail(-2, "fsr_conv3x3: statistics are not available together with pixel shuffle");
   if ((stats || preact || dact_mask) && (d->cout % 16 != 0 || (d->out_f32 && d->dtype != FSR_F32)))
     return fsr_fail(-2, "fsr_conv3x3: statistics / pre-activation / mask tensors need cout %% 16 == 0 and a `dtype` output");

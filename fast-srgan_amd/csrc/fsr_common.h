@@ -297,6 +297,35 @@ __device__ __forceinline__ unsigned char image_u8(float y) {
   return (unsigned char)w;
 }
 
+// ---- I420 output of a 3-channel tanh head (FSR_OUT_I420; the colour contract is DESIGN.md §6c).  A lane holds the (R, G, B) tanh
+// values t[m][c] of two vertically adjacent pixels (rows 2k and 2k + 1, m = 0, 1) of one column; the lane `lane ^ 1` holds the
+// neighbouring column of the same 2x2 block.  Every lane of the wave must call this (the shuffle), stores are guarded by the caller.
+// Out: the two pixels' Y codes, and the block's Cb / Cr codes -- the mean of E_C over the block, C420jpeg siting -- in both lanes.
+//   c = clamp((t + 1) / 2, 0, 1);  E_Y = Kr R + Kg G + Kb B;  E_Cb = (B - E_Y) / (2 (1 - Kb));  E_Cr = (R - E_Y) / (2 (1 - Kr))
+//   limited: Y = 16 + 219 E_Y, C = 128 + 224 E_C;  full: Y = 255 E_Y, C = 128 + 255 E_C;  code = clamp(floor(v + 0.5), 0, 255)
+__device__ __forceinline__ unsigned char yuv_code(float v) { return (unsigned char)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
+__device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, int full, unsigned char (&y)[2], unsigned char& cb,
+                                          unsigned char& cr) {
+  const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
+  const float kg = 1.f - kr - kb;
+  const float ys = full ? 255.f : 219.f, yo = full ? 0.f : 16.f, cs = full ? 255.f : 224.f;
+  float sb = 0.f, sr = 0.f;   // sums of B - E_Y and R - E_Y over the lane's two pixels
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const float r = fminf(fmaxf((t[m][0] + 1.f) * 0.5f, 0.f), 1.f);
+    const float g = fminf(fmaxf((t[m][1] + 1.f) * 0.5f, 0.f), 1.f);
+    const float b = fminf(fmaxf((t[m][2] + 1.f) * 0.5f, 0.f), 1.f);
+    const float ey = kr * r + kg * g + kb * b;
+    y[m] = yuv_code(yo + ys * ey);
+    sb += b - ey;
+    sr += r - ey;
+  }
+  sb += __shfl_xor(sb, 1, 64);
+  sr += __shfl_xor(sr, 1, 64);
+  cb = yuv_code(128.f + cs * (sb * 0.25f / (2.f * (1.f - kb))));
+  cr = yuv_code(128.f + cs * (sr * 0.25f / (2.f * (1.f - kr))));
+}
+
 // sum over the 64 lanes of a wave; every lane gets the total
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -7,6 +7,7 @@ TRUNCATING uint8 cast (:53-56) -- in the head kernel's epilogue.  Frames travel 
 batched and pipelined (InferencePipeline); decoding / encoding runs in worker threads.
 """
 import os
+import sys
 from argparse import ArgumentParser
 
 import numpy as np
@@ -14,6 +15,7 @@ import torch
 
 from .config import load_config
 from .model import Generator
+from .ops import i420_frame_bytes
 
 parser = ArgumentParser("Real Time Image Super Resolution")
 parser.add_argument("--image_dir", default=None, required=True, type=str)
@@ -47,7 +49,9 @@ class InferencePipeline:
       copy stream   : D2H of the finished uint8 frames (2.8 MB per 720p frame, 4x less than floats) into pinned memory,
                       overlapped with the next batch's compute (`depth` staging slots, each with its own graph)
     Frames are bucketed by shape; one set of graphs per (H, W), built lazily and kept for the most recently used shapes
-    only.  `run` yields results in input order."""
+    only.  `run` yields results in input order.
+    Video: `run_yuv420` takes I420 payloads (planar YUV 4:2:0, Generator.forward_yuv420) through the same staging, slots and
+    streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W)."""
 
     def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4):
         """copy=False: `run` yields VIEWS of the pinned result buffers (valid until `depth` more batches have been
@@ -80,9 +84,9 @@ class InferencePipeline:
                 torch.cuda.synchronize(self.device)
                 torch.cuda.empty_cache()
 
-    def _slot(self, h, w, j):
-        """Slot j of the plan for (h, w), created on first use."""
-        key = (h, w)
+    def _slot(self, fmt, j):
+        """Slot j of the plan for the frame format `fmt` (_Format), created on first use."""
+        key = fmt.key
         plan = self._plans.get(key)
         if plan is None:
             plan = self._plans[key] = [None] * self.depth
@@ -90,13 +94,14 @@ class InferencePipeline:
         if plan[j] is not None:
             return plan[j]
         sl = self._Slot()
-        sl.host_in = torch.empty((self.batch, h, w, 3), dtype=torch.uint8).pin_memory()
-        sl.x = torch.zeros((self.batch, h, w, 3), dtype=torch.uint8, device=self.device)
+        sl.host_in = torch.empty((self.batch,) + fmt.shape, dtype=torch.uint8).pin_memory()
+        sl.x = torch.zeros((self.batch,) + fmt.shape, dtype=torch.uint8, device=self.device)
+        sl.fwd = fmt.fwd
         with torch.no_grad():
             side = torch.cuda.Stream(device=self.device)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                y = self.model.forward_u8(sl.x)            # warm-up: creates every lazily allocated buffer
+                y = fmt.fwd(sl.x)                          # warm-up: creates every lazily allocated buffer
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             sl.graph = None
@@ -104,10 +109,11 @@ class InferencePipeline:
                 try:
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
-                        y = self.model.forward_u8(sl.x)
+                        y = fmt.fwd(sl.x)
                     sl.graph = g
                 except Exception as exc:  # noqa: BLE001 -- eager launches are always available
-                    print("InferencePipeline: hipGraph capture failed (%s: %s); eager launches" % (type(exc).__name__, exc))
+                    print("InferencePipeline: hipGraph capture failed (%s: %s); eager launches" % (type(exc).__name__, exc),
+                          file=sys.stderr)   # (stdout may be the video stream: video.py --output -)
                     torch.cuda.synchronize()
         sl.y = y
         sl.host_out = torch.empty(tuple(y.shape), dtype=torch.uint8).pin_memory()
@@ -121,11 +127,11 @@ class InferencePipeline:
         return sl
 
     @torch.no_grad()
-    def _eager(self, frames):
+    def _eager(self, fmt, frames):
         """A handful of frames of one shape (fewer than a batch): one eager launch at their TRUE count -- no staging plan, no
         graph capture, no padding of the batch with repeated frames."""
-        x = torch.from_numpy(np.stack([np.ascontiguousarray(f) for f in frames])).to(self.device)
-        y = self.model.forward_u8(x).cpu().numpy()
+        x = torch.from_numpy(np.stack([np.ascontiguousarray(f).reshape(fmt.shape) for f in frames])).to(self.device)
+        y = fmt.fwd(x).cpu().numpy()
         return [y[i] for i in range(len(frames))]
 
     @torch.no_grad()
@@ -133,14 +139,14 @@ class InferencePipeline:
         """Enqueue one batch on slot `sl` (its previous results have been collected): nothing here waits for the device."""
         n = len(frames)
         for i, f in enumerate(frames):
-            np.copyto(sl.host_in_np[i], f)
+            np.copyto(sl.host_in_np[i], np.asarray(f).reshape(sl.host_in_np.shape[1:]))
         assert n == self.batch       # (ragged tails run eagerly: InferencePipeline.run)
         main = torch.cuda.current_stream()
         sl.x.copy_(sl.host_in, non_blocking=True)
         if sl.graph is not None:
             sl.graph.replay()
         else:
-            sl.y = self.model.forward_u8(sl.x)
+            sl.y = sl.fwd(sl.x)
         sl.done.record(main)
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(sl.done)
@@ -155,11 +161,32 @@ class InferencePipeline:
         sl.pending = None
         return out
 
+    class _Format:
+        """What a plan is built for: its key in `_plans`, the shape of one input frame, and the device forward of a batch."""
+
+        def __init__(self, key, shape, fwd):
+            self.key, self.shape, self.fwd = key, shape, fwd
+
     def run(self, frames):
         """frames: iterable of uint8 (H,W,3) arrays, all of ONE shape per call (use `run_mixed` otherwise).  Yields uint8
         (4H,4W,3) arrays in order.  Full batches go through the pipelined slots; a ragged tail runs eagerly at its true size."""
+        return self._run(frames, None)
+
+    def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None):
+        """frames: iterable of I420 payloads of h x w (uint8 arrays or bytes of ops.i420_frame_bytes(h, w) each).  Yields the
+        uint8 I420 payloads of the super-resolved frames (Generator.forward_yuv420 with these colour parameters) in order,
+        batched and pipelined exactly as `run`."""
+        colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
+                      out_full_range=bool(full_range if out_full_range is None else out_full_range))
+        model = self.model
+        fmt = self._Format(("i420", h, w) + tuple(colour.values()), (i420_frame_bytes(h, w),),
+                           lambda x: model.forward_yuv420(x, h, w, **colour))
+        return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
+                          for f in frames), fmt)
+
+    def _run(self, frames, fmt):
         it = iter(frames)
-        hw, k, inflight = None, 0, []
+        k, inflight = 0, []
         while True:
             chunk = []
             for f in it:
@@ -168,15 +195,16 @@ class InferencePipeline:
                     break
             if not chunk:
                 break
-            if hw is None:
-                hw = (chunk[0].shape[0], chunk[0].shape[1])
+            if fmt is None:                       # RGB frames: plans keyed by (H, W)
+                h, w = chunk[0].shape[0], chunk[0].shape[1]
+                fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8)
             if len(chunk) < self.batch:           # the tail (or a bucket smaller than one batch)
                 for sl in inflight:
                     yield from self._collect(sl)
                 inflight = []
-                yield from self._eager(chunk)
+                yield from self._eager(fmt, chunk)
                 break
-            sl = self._slot(hw[0], hw[1], k % self.depth)
+            sl = self._slot(fmt, k % self.depth)
             if sl.pending is not None:
                 inflight.remove(sl)
                 yield from self._collect(sl)

@@ -81,6 +81,7 @@ class Generator(torch.nn.Module):
         self._cfg_up = ops.ConvCfg(cd, act=L.ACT_PRELU, pixel_shuffle=True)
         self._cfg_head = ops.ConvCfg(cd, tanh_head=True)
         self._cfg_head_u8 = ops.ConvCfg(cd, tanh_head=True, u8_head=True)
+        self._cfg_head_i420 = {}      # (matrix code, full range) -> ConvCfg of the I420 head
 
     def forward_u8(self, frames):
         """Inference on raw frames (inference.py:47-57 without the host round trips): (N,H,W,3) uint8 in, (N,4H,4W,3) uint8
@@ -89,6 +90,19 @@ class Generator(torch.nn.Module):
         floats."""
         with torch.no_grad():
             return self._forward(ops.u8_to_image(frames), self._cfg_head_u8)
+
+    def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None):
+        """Video inference on planar YUV 4:2:0 frames: (N, bytes) uint8 I420 payloads of h x w (odd sizes legal) in, (N, bytes)
+        uint8 I420 payloads of (s h) x (s w) out, s = 2 ** n_upsample.  The input is decoded on the device (matrix "bt601" /
+        "bt709", limited or full range, chroma `siting` "jpeg" or "mpeg2") into the generator's [-1, 1] RGB; the head's epilogue
+        encodes its float tanh output to Y, Cb, Cr planes (C420jpeg siting) in the output pair (out_matrix, out_full_range),
+        which defaults to the input's.  The colour contract is DESIGN.md §6c."""
+        key = (ops.yuv_matrix_code(out_matrix or matrix), int(bool(full_range if out_full_range is None else out_full_range)))
+        cfg = self._cfg_head_i420.get(key)
+        if cfg is None:
+            cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
+        with torch.no_grad():
+            return self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range), cfg)
 
     def forward(self, x):
         return self._forward(x, self._cfg_head)

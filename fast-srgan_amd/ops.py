@@ -462,9 +462,12 @@ class _on_wgrad_stream:
 # ---------------------------------------------------------------------------------- raw launches
 def conv3x3_raw(cd, x, wpk, cout, *, mode=L.CONV_FWD, out_hw=None, stride=1, bias=None, act=L.ACT_NONE, slope=0.0,
                 prelu=None, oscale=None, pixel_shuffle=False, in_pixel_shuffled=False, out_f32=False, want_stats=False,
-                want_preact=False, alg_k=None, dact_mask=None, dact_slope=0.0, out_u8=False, pool2=False, dact_add=False, dact_bits=False):
+                want_preact=False, alg_k=None, dact_mask=None, dact_slope=0.0, out_u8=False, pool2=False, dact_add=False, dact_bits=False,
+                out_i420=None):
     """One fsr_conv3x3 launch.  x: (N,IH,IW,Cin) [or its depth-to-space form when in_pixel_shuffled].
     out_u8 (tanh heads): the output is the finished uint8 HWC image of inference.py:53-56.
+    out_i420 = (matrix, full_range) (3-channel tanh heads, even output extents): the output is (N, OH*OW*3/2) uint8, the I420
+    planes of the RGB frame per image (FSR_OUT_I420).
     pool2 (no-grad passes): the output is MaxPool2d(2,2) of the activated result; the full-resolution tensor is never written.
     dact_add: `dact_mask` is ADDED to the result (the gradient of a skip connection) instead of gating it.
     dact_bits: `dact_mask` is the packed sign-bit tensor (N,OH,OW,Cout/8) uint8 of the producing layer's output (stride-2 data gradients)."""
@@ -480,13 +483,17 @@ def conv3x3_raw(cd, x, wpk, cout, *, mode=L.CONV_FWD, out_hw=None, stride=1, bia
         oh, ow = (ih - 1) // stride + 1, (iw - 1) // stride + 1
     else:
         oh, ow = out_hw
-    odt = torch.uint8 if out_u8 else (torch.float32 if out_f32 else cd.torch_dtype)
+    odt = torch.uint8 if (out_u8 or out_i420) else (torch.float32 if out_f32 else cd.torch_dtype)
     oshape = (n, 2 * oh, 2 * ow, cout // 4) if pixel_shuffle else ((n, oh // 2, ow // 2, cout) if pool2 else (n, oh, ow, cout))
+    if out_i420:
+        oshape = (n, oh * ow * 3 // 2)
     out = _empty(oshape, odt, x.device)
     pre = _empty(oshape, odt, x.device) if want_preact else None
     stats = _assigned((n, cout, 2), x.device) if want_stats else None
+    okind = L.OUT_I420 if out_i420 else (L.OUT_U8 if out_u8 else int(out_f32))
+    yuv = out_i420 or (0, 0)
     d = L.ConvDesc(cd.code, mode, n, ih, iw, cin, oh, ow, cout, stride, act, float(slope), int(pixel_shuffle),
-                   int(in_pixel_shuffled), L.OUT_U8 if out_u8 else int(out_f32), int(pool2), 2 if dact_bits else int(bool(dact_add)), 0)
+                   int(in_pixel_shuffled), okind, int(pool2), 2 if dact_bits else int(bool(dact_add)), 0, int(yuv[0]), int(yuv[1]))
     if isinstance(wpk, FilterSpec):     # pack in the layout the kernel this launch dispatches reads
         opt = ((L.OPT_BIAS if bias is not None else 0) | (L.OPT_PRELU if prelu is not None else 0) | (L.OPT_OSCALE if oscale is not None else 0)
                | (L.OPT_MASK if dact_mask is not None else 0) | (L.OPT_PREACT if want_preact else 0) | (L.OPT_STATS if want_stats else 0))
@@ -576,8 +583,9 @@ class ConvCfg:
 
     def __init__(self, cd, *, stride=1, act=L.ACT_NONE, slope=0.0, pixel_shuffle=False, stats=False, image_in=False,
                  in_scale=(1.0, 1.0, 1.0), in_shift=(0.0, 0.0, 0.0), tanh_head=False, input_act_bwd=None,
-                 act_bwd_by_consumer=False, u8_head=False, pool_after=False, n_alias=0, emit_signs=False):
+                 act_bwd_by_consumer=False, u8_head=False, pool_after=False, n_alias=0, emit_signs=False, i420_head=None):
         # u8_head (inference only, with tanh_head): the head stores the finished uint8 HWC frame instead of float
+        # i420_head = (matrix, full_range) (inference only, with tanh_head): the head stores the I420 planes of the frame
         # input_act_bwd = slope: the data-gradient launch also applies the backward of the ReLU (0.0) / LeakyReLU
         #   that produced this conv's input (the mask is the saved input itself), so the tensor it returns is
         #   already the producer's pre-activation gradient;
@@ -589,6 +597,7 @@ class ConvCfg:
         self.pixel_shuffle, self.stats, self.image_in = pixel_shuffle, stats, image_in
         self.in_scale, self.in_shift, self.tanh_head = in_scale, in_shift, tanh_head
         self.u8_head = u8_head and tanh_head
+        self.i420_head = i420_head if tanh_head else None
         # pool_after (no-grad passes only): the MaxPool2d(2,2) that follows this conv + ReLU is taken in the epilogue and
         # only the pooled tensor is stored (the full-resolution tensor is what a backward pass would need)
         self.pool_after = pool_after
@@ -634,15 +643,15 @@ class Conv3x3Fn(torch.autograd.Function):
         cin_pad = xin.shape[3]
         wpk = FilterSpec(weight, L.PACK_FWD_PS if cfg.pixel_shuffle else L.PACK_FWD, cin_pad)
         training = ctx.grad_on and any(ctx.needs_input_grad)
-        if (cfg.u8_head or cfg.pool_after) and training:
-            raise L.FsrError("the uint8 head / fused max-pool epilogues are inference-only: they have no gradient")
+        if (cfg.u8_head or cfg.i420_head or cfg.pool_after) and training:
+            raise L.FsrError("the uint8 / I420 head and fused max-pool epilogues are inference-only: they have no gradient")
         act = L.ACT_TANH if cfg.tanh_head else cfg.act
         want_pre = training and act == L.ACT_PRELU
         b32 = bias if bias is None or bias.dtype == torch.float32 else bias.float()
         out, pre, stats = conv3x3_raw(cd, xin, wpk, cout, stride=cfg.stride, bias=b32, act=act, slope=cfg.slope,
                                       prelu=prelu, pixel_shuffle=cfg.pixel_shuffle, out_f32=cfg.tanh_head,
                                       want_stats=cfg.stats, want_preact=want_pre, alg_k=cin, out_u8=cfg.u8_head,
-                                      pool2=cfg.pool_after)
+                                      pool2=cfg.pool_after, out_i420=cfg.i420_head)
         ctx.cfg = cfg
         ctx.dims = (cout, cin, tuple(xin.shape))
         ctx.has_bias = bias is not None
@@ -653,8 +662,8 @@ class Conv3x3Fn(torch.autograd.Function):
             stats = torch.empty(0, device=out.device)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)    # no zero-filled gradient tensor for the statistics output per backward call
-        if cfg.u8_head:
-            return out, stats               # (N,H,W,3) uint8: already the frame layout inference.py:55 permutes to
+        if cfg.u8_head or cfg.i420_head:
+            return out, stats               # (N,H,W,3) uint8: already the frame layout inference.py:55 permutes to; I420: (N, bytes)
         if cfg.tanh_head:
             return out.permute(0, 3, 1, 2), stats
         if cfg.n_alias:
@@ -1104,4 +1113,36 @@ def u8_to_image(frames):
         raise ValueError("u8_to_image expects a contiguous (N,H,W,3) uint8 tensor")
     img = torch.empty(frames.shape, dtype=torch.float32, device=frames.device)
     L.check(L.lib().fsr_u8_to_image(_p(frames), _p(img), frames.numel(), _stream()), "fsr_u8_to_image")
+    return img.permute(0, 3, 1, 2)
+
+
+def i420_frame_bytes(h, w):
+    """Bytes of one I420 payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) each."""
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+YUV_MATRICES = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
+CHROMA_SITINGS = {"jpeg": L.SITING_JPEG, "mpeg2": L.SITING_MPEG2}
+
+
+def yuv_matrix_code(matrix):
+    if matrix not in YUV_MATRICES:
+        raise ValueError("colour matrix must be one of %s, got %r" % (sorted(YUV_MATRICES), matrix))
+    return YUV_MATRICES[matrix]
+
+
+def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False):
+    """(N, i420_frame_bytes(h, w)) uint8 I420 payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1 of the
+    decoded RGB; chroma upsampled bilinearly at `siting` "jpeg" (centred) or "mpeg2" (co-sited horizontally); DESIGN.md
+    "Video"), the layout u8_to_image returns."""
+    _check_dev(frames)
+    if siting not in CHROMA_SITINGS:
+        raise ValueError("chroma siting must be one of %s, got %r" % (sorted(CHROMA_SITINGS), siting))
+    if (frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != i420_frame_bytes(h, w) or not frames.is_contiguous()):
+        raise ValueError("i420_to_image expects a contiguous (N, %d) uint8 tensor of %dx%d I420 frames, got %s %s"
+                         % (i420_frame_bytes(h, w), w, h, frames.dtype, tuple(frames.shape)))
+    n = frames.shape[0]
+    img = torch.empty((n, h, w, 3), dtype=torch.float32, device=frames.device)
+    L.check(L.lib().fsr_i420_to_image(_p(frames), _p(img), n, h, w, CHROMA_SITINGS[siting], yuv_matrix_code(matrix), int(bool(full_range)),
+                                      _stream()), "fsr_i420_to_image")
     return img.permute(0, 3, 1, 2)

@@ -1,0 +1,188 @@
+"""`python video.py --input IN --output OUT`: super-resolution of a YUV4MPEG2 (Y4M) stream of I420 frames.
+
+    ffmpeg -i in.mp4 -f yuv4mpegpipe - | python video.py --input - --output - | ffmpeg -i - -c:v libx264 out.mp4
+
+Y4M is the plain container of uncompressed frames that `ffmpeg -f yuv4mpegpipe` reads and writes on pipes, so no codec
+library is involved.  Frames stay planar YUV 4:2:0 end to end: the device converts the input to the generator's [-1, 1]
+RGB (fsr_i420_to_image) and the head's epilogue stores finished I420 planes (FSR_OUT_I420), so the host only moves bytes
+-- 1.5 per output pixel instead of 3.  The colour contract (matrices, ranges, chroma siting) is DESIGN.md §6c.
+
+Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
+stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
+device batch at a time: a stream of any length passes through a pipe.
+"""
+import sys
+import time
+from argparse import ArgumentParser
+
+import numpy as np
+
+from .ops import i420_frame_bytes
+
+MATRICES = ("bt601", "bt709")
+SITINGS = ("jpeg", "mpeg2")
+
+
+class Y4MError(ValueError):
+    pass
+
+
+# colour-space tags (`C...`) this reader takes, and the chroma siting each declares; a missing tag means C420jpeg
+_ACCEPTED_C = {"420jpeg": "jpeg", "420": "jpeg", "420mpeg2": "mpeg2"}
+_REJECTED_C = ("420paldv", "411", "422", "444", "444alpha", "mono")
+
+
+class Y4MReader:
+    """Streaming reader: parses the stream header on construction, then `frames()` yields one uint8 payload
+    (i420_frame_bytes(height, width) bytes, a numpy array) per FRAME, reading only that frame from the file."""
+
+    def __init__(self, f):
+        self.f = f
+        line = f.readline()
+        if not line.startswith(b"YUV4MPEG2"):
+            raise Y4MError("Y4M: the stream does not start with the YUV4MPEG2 signature")
+        if not line.endswith(b"\n"):
+            raise Y4MError("Y4M: the stream header is not terminated")
+        self.width = self.height = None
+        self.frame_rate = self.aspect = self.interlace = None
+        self.siting = "jpeg"
+        self.colour_range = None          # XCOLORRANGE: "full" / "limited", or None when the stream does not say
+        self.x_tags = []
+        for tok in line[len(b"YUV4MPEG2"):].decode("ascii", "replace").split():
+            key, val = tok[0], tok[1:]
+            if key == "W":
+                self.width = int(val)
+            elif key == "H":
+                self.height = int(val)
+            elif key == "F":
+                self.frame_rate = val
+            elif key == "A":
+                self.aspect = val
+            elif key == "I":
+                if val in ("t", "b", "m"):
+                    raise Y4MError("Y4M: interlaced streams are not supported (tag 'I%s'); deinterlace first" % val)
+                self.interlace = val
+            elif key == "C":
+                self.siting = self._colour_space(val)
+            elif key == "X":
+                self.x_tags.append(val)
+                if val.upper().startswith("COLORRANGE="):
+                    r = val.split("=", 1)[1].upper()
+                    if r not in ("FULL", "LIMITED"):
+                        raise Y4MError("Y4M: unknown tag value 'X%s' (XCOLORRANGE is FULL or LIMITED)" % val)
+                    self.colour_range = r.lower()
+        if not self.width or not self.height or self.width <= 0 or self.height <= 0:
+            raise Y4MError("Y4M: the stream header lacks the frame size (tags 'W' and 'H')")
+        self.frame_bytes = i420_frame_bytes(self.height, self.width)
+
+    @staticmethod
+    def _colour_space(val):
+        if val in _ACCEPTED_C:
+            return _ACCEPTED_C[val]
+        if val in _REJECTED_C:
+            raise Y4MError("Y4M: colour space 'C%s' is not supported (4:2:0 8-bit only: C420jpeg, C420mpeg2)" % val)
+        if "p" in val and val.split("p")[-1].isdigit():
+            raise Y4MError("Y4M: colour space 'C%s' is deeper than 8 bits (4:2:0 8-bit only)" % val)
+        raise Y4MError("Y4M: unknown colour space 'C%s' (4:2:0 8-bit only: C420jpeg, C420mpeg2)" % val)
+
+    def frames(self):
+        idx = 0
+        while True:
+            line = self.f.readline()
+            if not line:
+                return
+            if not line.startswith(b"FRAME") or not line.endswith(b"\n"):
+                raise Y4MError("Y4M: frame %d does not start with a FRAME line" % idx)
+            buf = bytearray(self.frame_bytes)
+            view, got = memoryview(buf), 0
+            while got < self.frame_bytes:
+                k = self.f.readinto(view[got:])
+                if not k:
+                    raise Y4MError("Y4M: frame %d is truncated (%d of %d bytes)" % (idx, got, self.frame_bytes))
+                got += k
+            yield np.frombuffer(buf, dtype=np.uint8)
+            idx += 1
+
+
+class Y4MWriter:
+    """Writes the stream header on construction (C420jpeg, XCOLORRANGE of the output range), then one FRAME per payload."""
+
+    def __init__(self, f, width, height, frame_rate=None, aspect=None, interlace=None, full_range=False):
+        self.f = f
+        self.frame_bytes = i420_frame_bytes(height, width)
+        tags = ["W%d" % width, "H%d" % height]
+        if frame_rate is not None:
+            tags.append("F" + frame_rate)
+        if interlace is not None:
+            tags.append("I" + interlace)
+        if aspect is not None:
+            tags.append("A" + aspect)
+        tags += ["C420jpeg", "XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")]
+        f.write(("YUV4MPEG2 " + " ".join(tags) + "\n").encode("ascii"))
+
+    def write_frame(self, payload):
+        payload = memoryview(np.ascontiguousarray(payload)).cast("B")
+        if payload.nbytes != self.frame_bytes:
+            raise Y4MError("Y4M: a frame of %d bytes does not match the stream's %d" % (payload.nbytes, self.frame_bytes))
+        self.f.write(b"FRAME\n")
+        self.f.write(payload)
+
+
+parser = ArgumentParser("Real Time Video Super Resolution (Y4M, I420)")
+parser.add_argument("--input", required=True, type=str, help="Y4M stream, or - for stdin")
+parser.add_argument("--output", required=True, type=str, help="Y4M stream, or - for stdout")
+parser.add_argument("--compute_dtype", default=None, choices=["bf16", "f16", "x3", "x3v", "f32"], help="kernel precision")
+parser.add_argument("--batch", default=8, type=int, help="frames per device batch")
+parser.add_argument("--matrix", default="bt601", choices=MATRICES, help="colour matrix of the input")
+parser.add_argument("--range", default="limited", choices=["limited", "full"], help="input range (XCOLORRANGE overrides it)")
+parser.add_argument("--out_matrix", default=None, choices=MATRICES, help="colour matrix of the output (default: the input's)")
+parser.add_argument("--out_range", default=None, choices=["limited", "full"], help="output range (default: the input's)")
+
+
+def _status(msg):
+    print(msg, file=sys.stderr, flush=True)
+
+
+def main(argv=None):
+    import torch
+
+    from .config import load_config
+    from .inference import InferencePipeline, load_generator
+    args = parser.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("fast-srgan_amd runs on an MI355X only: no GPU is visible")
+    fin = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
+    fout = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
+    try:
+        reader = Y4MReader(fin)
+        full = (reader.colour_range or args.range) == "full"
+        out_full = full if args.out_range is None else args.out_range == "full"
+        out_matrix = args.out_matrix or args.matrix
+        config = load_config("configs/config.yaml")
+        model = load_generator(config, "models/model.pt", "cuda", args.compute_dtype)
+        s = 2 ** len(model.upsampling)
+        h, w = reader.height, reader.width
+        _status("video: %dx%d -> %dx%d, %s %s -> %s %s, chroma siting %s" % (
+            w, h, s * w, s * h, args.matrix, "full" if full else "limited", out_matrix, "full" if out_full else "limited", reader.siting))
+        writer = Y4MWriter(fout, s * w, s * h, reader.frame_rate, reader.aspect, reader.interlace, out_full)
+        pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False)
+        n, t0, t1 = 0, time.perf_counter(), None
+        for y in pipe.run_yuv420(reader.frames(), h, w, siting=reader.siting, matrix=args.matrix, full_range=full,
+                                 out_matrix=out_matrix, out_full_range=out_full):
+            writer.write_frame(y)       # (a view of the pinned result buffer: written before the slot is reused)
+            n += 1
+            if n == args.batch:
+                t1 = time.perf_counter()   # the first batch carries the plan's warm-up and graph capture
+        fout.flush()
+        t2 = time.perf_counter()
+        steady = "%.1f fps after the first batch" % ((n - args.batch) / (t2 - t1)) if t1 is not None and n > args.batch else "-"
+        _status("video: %d frames in %.3f s (%s)" % (n, t2 - t0, steady))
+    finally:
+        if fin is not sys.stdin.buffer:
+            fin.close()
+        if fout is not sys.stdout.buffer:
+            fout.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -46,13 +46,15 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 10
+#define FSR_ABI_VERSION 11
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
 enum { FSR_CONV_FWD = 0, FSR_CONV_DGRAD = 1 };
 enum { FSR_PACK_FWD = 0, FSR_PACK_FWD_PS = 1, FSR_PACK_DGRAD = 2, FSR_PACK_DGRAD_PS = 3 };
-enum { FSR_OUT_DTYPE = 0, FSR_OUT_F32 = 1, FSR_OUT_U8 = 2 };   /* fsr_conv_desc.out_f32 */
+enum { FSR_OUT_DTYPE = 0, FSR_OUT_F32 = 1, FSR_OUT_U8 = 2, FSR_OUT_I420 = 3 };   /* fsr_conv_desc.out_f32 */
+enum { FSR_YUV_BT601 = 0, FSR_YUV_BT709 = 1 };             /* fsr_conv_desc.yuv_matrix, fsr_i420_to_image */
+enum { FSR_SITING_JPEG = 0, FSR_SITING_MPEG2 = 1 };        /* chroma siting of fsr_i420_to_image's input */
 
 typedef void* fsr_stream_t; /* hipStream_t */
 
@@ -101,7 +103,10 @@ int fsr_pack_conv3x3_lin(int dtype, int mode, const float* w_oihw, int cout, int
  * out_f32: FSR_OUT_DTYPE (0): `dtype` output; FSR_OUT_F32 (1): store float whatever `dtype` is (3-channel outputs:
  *   head images, image gradients); FSR_OUT_U8 (2, FSR_ACT_TANH heads, forward): store the uint8 HWC image
  *   (unsigned char)(((tanh(z) + 1) / 2) * 255) -- inference.py:53-56's post-processing with its truncating cast,
- *   out [n,oh,ow,cout] bytes (cout = 3: the finished RGB frame).
+ *   out [n,oh,ow,cout] bytes (cout = 3: the finished RGB frame); FSR_OUT_I420 (3, FSR_ACT_TANH heads, forward, stride 1,
+ *   cout = 3, even oh and ow, no statistics / pre-activation / mask / scale tensors): store the I420 (planar YUV 4:2:0) frame of the
+ *   RGB head output -- per image the Y plane [oh][ow], then Cb and Cr [oh/2][ow/2] (oh * ow * 3 / 2 bytes, C420jpeg siting:
+ *   chroma is the mean of the 2x2 block), matrix and range from yuv_matrix / yuv_full_range.
  * pool2 (inference / no-grad passes of vgg19.features, model.py:8,191): the kernel's epilogue takes the 2x2 maximum of the
  *   activated outputs and stores only the pooled tensor -- the full-resolution tensor, which only a backward pass would
  *   read, is never written.  oh, ow even; cout %% 16 == 0; no stats / preact / mask tensors.
@@ -134,6 +139,8 @@ typedef struct fsr_conv_desc {
                          gradients, 16-bit dtypes): it is the PACKED SIGN-BIT tensor [n][oh][ow][cout / 8] of the producing layer's output
                          (bit c & 7 of byte c >> 3 = output > 0: fsr_conv3x3_c3_fwd's `signs`), gating like 0 at a sixteenth of the bytes */
   int pack_lin; /* 0: packed_w is fsr_pack_conv3x3's layout; 64 / 128: fsr_pack_conv3x3_lin's with that block (must equal fsr_conv3x3_pack_block) */
+  int yuv_matrix;     /* FSR_OUT_I420: FSR_YUV_BT601 or FSR_YUV_BT709 (ignored by the other output kinds) */
+  int yuv_full_range; /* FSR_OUT_I420: 0 limited range (Y 16..235, C 16..240), 1 full range (0..255) */
 } fsr_conv_desc;
 
 /* Block size of the stage-contiguous filter pack (fsr_pack_conv3x3_lin) that the kernel fsr_conv3x3 would dispatch for `desc`
@@ -229,6 +236,13 @@ int fsr_tanh_bwd_to_nhwc(int dtype, const float* g, long long sn, long long sc, 
 /* uint8 HWC frames [n,h,w,3] -> float [n,h,w,3], x / 127.5 - 1 (inference.py:48: the first-layer kernels read the result
  * in place as an NCHW-shaped tensor of strides (3hw, 1, 3w, 3)). */
 int fsr_u8_to_image(const uint8_t* frames, float* img, long long count, fsr_stream_t stream);
+
+/* I420 frames (n contiguous payloads: Y [h][w], then Cb and Cr [(h+1)/2][(w+1)/2]; odd h and w are legal) -> float
+ * [n,h,w,3] = 2 c - 1 of the decoded RGB c in [0, 1] -- the layout fsr_u8_to_image writes.  Chroma is upsampled bilinearly
+ * (edge clamp) at the siting FSR_SITING_JPEG (centred on both axes) or FSR_SITING_MPEG2 (co-sited horizontally); `matrix`
+ * FSR_YUV_BT601 / FSR_YUV_BT709, full_range 0 / 1. */
+int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
+                      fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ first-layer convolutions straight from the image
  * Conv2d(3 -> cout, k3, p1) of Generator.neck (model.py:75-78), Discriminator.neck (model.py:143-146) and
