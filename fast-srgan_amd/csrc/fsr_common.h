@@ -304,26 +304,45 @@ __device__ __forceinline__ unsigned char image_u8(float y) {
 //   c = clamp((t + 1) / 2, 0, 1);  E_Y = Kr R + Kg G + Kb B;  E_Cb = (B - E_Y) / (2 (1 - Kb));  E_Cr = (R - E_Y) / (2 (1 - Kr))
 //   limited: Y = 16 + 219 E_Y, C = 128 + 224 E_C;  full: Y = 255 E_Y, C = 128 + 255 E_C;  code = clamp(floor(v + 0.5), 0, 255)
 __device__ __forceinline__ unsigned char yuv_code(float v) { return (unsigned char)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
-__device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, int full, unsigned char (&y)[2], unsigned char& cb,
-                                          unsigned char& cr) {
+// The per-pixel and per-block parts, shared with the resampler (resample.hip), whose threads hold whole 2x2 blocks:
+//   i420_pixel : clamped (R, G, B) in [0, 1] -> the pixel's Y code; db = B - E_Y, dr = R - E_Y
+//   i420_chroma: the sums of db and dr over the four pixels of a block (the vertical pair first, then the two columns) -> Cb, Cr codes
+struct i420_coef {
+  float kr, kg, kb, ys, yo, cs;
+};
+__device__ __forceinline__ i420_coef i420_coefs(int matrix, int full) {
   const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
   const float kg = 1.f - kr - kb;
   const float ys = full ? 255.f : 219.f, yo = full ? 0.f : 16.f, cs = full ? 255.f : 224.f;
+  return i420_coef{kr, kg, kb, ys, yo, cs};
+}
+__device__ __forceinline__ unsigned char i420_pixel(const i420_coef& k, float r, float g, float b, float& db, float& dr) {
+  const float ey = k.kr * r + k.kg * g + k.kb * b;
+  db = b - ey;
+  dr = r - ey;
+  return yuv_code(k.yo + k.ys * ey);
+}
+__device__ __forceinline__ void i420_chroma(const i420_coef& k, float sb, float sr, unsigned char& cb, unsigned char& cr) {
+  cb = yuv_code(128.f + k.cs * (sb * 0.25f / (2.f * (1.f - k.kb))));
+  cr = yuv_code(128.f + k.cs * (sr * 0.25f / (2.f * (1.f - k.kr))));
+}
+__device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, int full, unsigned char (&y)[2], unsigned char& cb,
+                                          unsigned char& cr) {
+  const i420_coef k = i420_coefs(matrix, full);
   float sb = 0.f, sr = 0.f;   // sums of B - E_Y and R - E_Y over the lane's two pixels
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     const float r = fminf(fmaxf((t[m][0] + 1.f) * 0.5f, 0.f), 1.f);
     const float g = fminf(fmaxf((t[m][1] + 1.f) * 0.5f, 0.f), 1.f);
     const float b = fminf(fmaxf((t[m][2] + 1.f) * 0.5f, 0.f), 1.f);
-    const float ey = kr * r + kg * g + kb * b;
-    y[m] = yuv_code(yo + ys * ey);
-    sb += b - ey;
-    sr += r - ey;
+    float db, dr;
+    y[m] = i420_pixel(k, r, g, b, db, dr);
+    sb += db;
+    sr += dr;
   }
   sb += __shfl_xor(sb, 1, 64);
   sr += __shfl_xor(sr, 1, 64);
-  cb = yuv_code(128.f + cs * (sb * 0.25f / (2.f * (1.f - kb))));
-  cr = yuv_code(128.f + cs * (sr * 0.25f / (2.f * (1.f - kr))));
+  i420_chroma(k, sb, sr, cb, cr);
 }
 
 // sum over the 64 lanes of a wave; every lane gets the total

@@ -6,6 +6,7 @@ case (:37-45), writes each result under the same basename (:57) and converts wit
 TRUNCATING uint8 cast (:53-56) -- in the head kernel's epilogue.  Frames travel as bytes in both directions and are
 batched and pipelined (InferencePipeline); decoding / encoding runs in worker threads.
 """
+import math
 import os
 import sys
 from argparse import ArgumentParser
@@ -22,6 +23,37 @@ parser.add_argument("--image_dir", default=None, required=True, type=str)
 parser.add_argument("--output_dir", default=None, required=True, type=str)
 parser.add_argument("--compute_dtype", default=None, choices=["bf16", "f16", "x3", "x3v", "f32"], help="extension: kernel precision")
 parser.add_argument("--batch", default=8, type=int, help="extension: frames per device batch (same-shape frames are batched)")
+_size_flags = parser.add_mutually_exclusive_group()
+_size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="extension: exact output size (default: 4x the input)")
+_size_flags.add_argument("--scale", default=None, type=float, help="extension: output size relative to the INPUT, e.g. 2 or 1.5")
+
+
+def resolve_out_size(h, w, size=None, scale=None, even=False):
+    """The (out_h, out_w) that `--size WxH` / `--scale S` ask for on an h x w input, or None when neither is given (the
+    network's native size).  `--size` is exact and puts the WIDTH first -- the only place that does; `--scale` is relative to
+    the input: round(S h) x round(S w), halves rounding up.  even (video: 4:2:0 chroma needs even extents): `--scale` results
+    are rounded to the nearest even number instead, and an odd `--size` is refused."""
+    if size is not None and scale is not None:
+        raise ValueError("--size and --scale are mutually exclusive")
+    if size is not None:
+        parts = str(size).lower().split("x")
+        if len(parts) != 2 or not all(p.strip().isdigit() for p in parts):
+            raise ValueError("--size must be WxH, e.g. 1920x1080, got %r" % (size,))
+        ow, oh = int(parts[0]), int(parts[1])
+        if ow <= 0 or oh <= 0:
+            raise ValueError("--size must be positive, got %r" % (size,))
+        if even and (ow % 2 or oh % 2):
+            raise ValueError("--size %dx%d is odd: a YUV 4:2:0 frame holds one chroma sample per 2x2 block of pixels, so the output "
+                             "width and height must be even" % (ow, oh))
+        return oh, ow
+    if scale is not None:
+        scale = float(scale)
+        if not scale > 0.0 or scale != scale or scale == float("inf"):
+            raise ValueError("--scale must be a positive number, got %r" % (scale,))
+        if even:
+            return tuple(max(2, 2 * int(math.floor(scale * d / 2.0 + 0.5))) for d in (h, w))
+        return tuple(max(1, int(math.floor(scale * d + 0.5))) for d in (h, w))
+    return None
 
 
 def load_generator(config, model_path, device="cuda", compute_dtype=None):
@@ -32,11 +64,11 @@ def load_generator(config, model_path, device="cuda", compute_dtype=None):
 
 
 @torch.no_grad()
-def super_resolve(model, lr_u8_hwc, device="cuda"):
+def super_resolve(model, lr_u8_hwc, device="cuda", out_size=None):
     """uint8 (H,W,3) -> uint8 (4H,4W,3), inference.py:48-56, one frame: bytes up, bytes down; the [-1,1] mapping and the
-    (y+1)/2*255 truncating cast run on the device (Generator.forward_u8)."""
+    (y+1)/2*255 truncating cast run on the device (Generator.forward_u8).  out_size = (out_h, out_w): that size instead."""
     frame = torch.from_numpy(np.ascontiguousarray(lr_u8_hwc)).unsqueeze(0).to(device)
-    return model.forward_u8(frame)[0].cpu().numpy()
+    return model.forward_u8(frame, out_size=out_size)[0].cpu().numpy()
 
 
 class InferencePipeline:
@@ -51,7 +83,10 @@ class InferencePipeline:
     Frames are bucketed by shape; one set of graphs per (H, W), built lazily and kept for the most recently used shapes
     only.  `run` yields results in input order.
     Video: `run_yuv420` takes I420 payloads (planar YUV 4:2:0, Generator.forward_yuv420) through the same staging, slots and
-    streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W)."""
+    streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W).
+    Output size: every run method takes out_size = (out_h, out_w) (Generator.forward_u8 / forward_yuv420: the fused resize
+    after the head, captured in the same graph).  Plans of a resized output append ("size", out_h, out_w) to the key of the
+    native plan, so both coexist; None or the native size IS the native plan."""
 
     def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4):
         """copy=False: `run` yields VIEWS of the pinned result buffers (valid until `depth` more batches have been
@@ -167,24 +202,35 @@ class InferencePipeline:
         def __init__(self, key, shape, fwd):
             self.key, self.shape, self.fwd = key, shape, fwd
 
-    def run(self, frames):
-        """frames: iterable of uint8 (H,W,3) arrays, all of ONE shape per call (use `run_mixed` otherwise).  Yields uint8
-        (4H,4W,3) arrays in order.  Full batches go through the pipelined slots; a ragged tail runs eagerly at its true size."""
-        return self._run(frames, None)
+    def _out_size(self, h, w, out_size):
+        """out_size normalised: None for the network's native size of an h x w input, else (out_h, out_w) as ints."""
+        if out_size is None:
+            return None
+        oh, ow = int(out_size[0]), int(out_size[1])
+        s = 2 ** len(self.model.upsampling)
+        return None if (oh, ow) == (s * h, s * w) else (oh, ow)
 
-    def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None):
+    def run(self, frames, out_size=None):
+        """frames: iterable of uint8 (H,W,3) arrays, all of ONE shape per call (use `run_mixed` otherwise).  Yields uint8
+        (4H,4W,3) arrays -- (out_h, out_w, 3) with out_size = (out_h, out_w) -- in order.  Full batches go through the pipelined
+        slots; a ragged tail runs eagerly at its true size."""
+        return self._run(frames, None, out_size)
+
+    def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
+                   out_size=None):
         """frames: iterable of I420 payloads of h x w (uint8 arrays or bytes of ops.i420_frame_bytes(h, w) each).  Yields the
         uint8 I420 payloads of the super-resolved frames (Generator.forward_yuv420 with these colour parameters) in order,
-        batched and pipelined exactly as `run`."""
+        batched and pipelined exactly as `run`.  out_size = (out_h, out_w), both even: payloads of that size."""
         colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
                       out_full_range=bool(full_range if out_full_range is None else out_full_range))
         model = self.model
-        fmt = self._Format(("i420", h, w) + tuple(colour.values()), (i420_frame_bytes(h, w),),
-                           lambda x: model.forward_yuv420(x, h, w, **colour))
+        out_size = self._out_size(h, w, out_size)
+        key = ("i420", h, w) + tuple(colour.values()) + (() if out_size is None else ("size",) + out_size)
+        fmt = self._Format(key, (i420_frame_bytes(h, w),), lambda x: model.forward_yuv420(x, h, w, out_size=out_size, **colour))
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)
 
-    def _run(self, frames, fmt):
+    def _run(self, frames, fmt, out_size=None):
         it = iter(frames)
         k, inflight = 0, []
         while True:
@@ -197,7 +243,11 @@ class InferencePipeline:
                 break
             if fmt is None:                       # RGB frames: plans keyed by (H, W)
                 h, w = chunk[0].shape[0], chunk[0].shape[1]
-                fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8)
+                size = self._out_size(h, w, out_size)
+                if size is None:
+                    fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8)
+                else:
+                    fmt = self._Format((h, w, "size") + size, (h, w, 3), lambda x, m=self.model, sz=size: m.forward_u8(x, out_size=sz))
             if len(chunk) < self.batch:           # the tail (or a bucket smaller than one batch)
                 for sl in inflight:
                     yield from self._collect(sl)
@@ -214,15 +264,17 @@ class InferencePipeline:
         for sl in inflight:
             yield from self._collect(sl)
 
-    def run_mixed(self, frames):
-        """Frames of any shapes: bucketed by (H, W), results returned as a list in input order."""
+    def run_mixed(self, frames, out_size=None):
+        """Frames of any shapes: bucketed by (H, W), results returned as a list in input order.  out_size: (out_h, out_w) for
+        every frame, or a function (h, w) -> (out_h, out_w) (or None: native) asked once per input shape."""
         frames = list(frames)
         out = [None] * len(frames)
         buckets = {}
         for i, f in enumerate(frames):
             buckets.setdefault((f.shape[0], f.shape[1]), []).append(i)
-        for idx in buckets.values():
-            for i, y in zip(idx, self.run(frames[j] for j in idx)):
+        for (h, w), idx in buckets.items():
+            size = out_size(h, w) if callable(out_size) else out_size
+            for i, y in zip(idx, self.run((frames[j] for j in idx), size)):
                 out[i] = y
         return out
 
@@ -243,6 +295,7 @@ def main(argv=None):
                          if x.lower().endswith(".png") or x.lower().endswith(".jpg") or x.lower().endswith("jpeg"))
     print(f"Found {len(image_paths)} to super resolve, starting...")
     pipe = InferencePipeline(model, device, batch=args.batch)
+    resolve_out_size(1, 1, args.size, args.scale)      # a malformed --size fails before any image is read
 
     def load(name):
         return np.array(Image.open(os.path.join(args.image_dir, name)).convert("RGB"))
@@ -256,7 +309,8 @@ def main(argv=None):
         for start in range(0, len(image_paths), window):
             names = image_paths[start:start + window]
             frames = list(pool.map(load, names))
-            saves = [pool.submit(save, n, y) for n, y in zip(names, pipe.run_mixed(frames))]
+            results = pipe.run_mixed(frames, lambda h, w: resolve_out_size(h, w, args.size, args.scale))
+            saves = [pool.submit(save, n, y) for n, y in zip(names, results)]
             for s_ in saves:
                 s_.result()
 

@@ -83,21 +83,47 @@ class Generator(torch.nn.Module):
         self._cfg_head_u8 = ops.ConvCfg(cd, tanh_head=True, u8_head=True)
         self._cfg_head_i420 = {}      # (matrix code, full range) -> ConvCfg of the I420 head
 
-    def forward_u8(self, frames):
+    def _native_size(self, h, w, out_size):
+        """True when out_size (None or (out_h, out_w)) is the size the network produces for an h x w input."""
+        if out_size is None:
+            return True
+        s = 2 ** len(self.upsampling)
+        oh, ow = out_size
+        if int(oh) != oh or int(ow) != ow or oh <= 0 or ow <= 0:
+            raise ValueError("out_size must be (out_h, out_w) of positive integers, got %r" % (out_size,))
+        return (int(oh), int(ow)) == (s * h, s * w)
+
+    def forward_u8(self, frames, out_size=None):
         """Inference on raw frames (inference.py:47-57 without the host round trips): (N,H,W,3) uint8 in, (N,4H,4W,3) uint8
         out.  The [-1,1] mapping (:48) is one small kernel in front of the neck; the head's epilogue applies :53-56
         ((y+1)/2 * 255, truncating cast) and stores bytes -- a 720p frame leaves the device as 2.8 MB instead of 11 MB of
-        floats."""
+        floats.
+        out_size = (out_h, out_w): frames of that size instead -- the float head output goes through one fused kernel, the
+        antialiased bicubic resize with the same truncating cast (ops.resample_image).  None or the native size:
+        the head's own epilogue, as before."""
         with torch.no_grad():
-            return self._forward(ops.u8_to_image(frames), self._cfg_head_u8)
+            if self._native_size(frames.shape[1], frames.shape[2], out_size):
+                return self._forward(ops.u8_to_image(frames), self._cfg_head_u8)
+            t = self._forward(ops.u8_to_image(frames), self._cfg_head)
+            return ops.resample_image(t.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "u8")
 
-    def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None):
+    def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
+                       out_size=None):
         """Video inference on planar YUV 4:2:0 frames: (N, bytes) uint8 I420 payloads of h x w (odd sizes legal) in, (N, bytes)
         uint8 I420 payloads of (s h) x (s w) out, s = 2 ** n_upsample.  The input is decoded on the device (matrix "bt601" /
         "bt709", limited or full range, chroma `siting` "jpeg" or "mpeg2") into the generator's [-1, 1] RGB; the head's epilogue
         encodes its float tanh output to Y, Cb, Cr planes (C420jpeg siting) in the output pair (out_matrix, out_full_range),
-        which defaults to the input's.  The colour contract is DESIGN.md §6c."""
-        key = (ops.yuv_matrix_code(out_matrix or matrix), int(bool(full_range if out_full_range is None else out_full_range)))
+        which defaults to the input's.  The colour contract is DESIGN.md §6c.
+        out_size = (out_h, out_w), both even: payloads of that size instead -- the float head output is resized (antialiased
+        bicubic) and encoded by one fused kernel (ops.resample_image).  None or the native size: the head's own
+        epilogue, as before."""
+        out_matrix = out_matrix or matrix
+        out_full = bool(full_range if out_full_range is None else out_full_range)
+        key = (ops.yuv_matrix_code(out_matrix), int(out_full))
+        if not self._native_size(h, w, out_size):
+            with torch.no_grad():
+                t = self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range), self._cfg_head)
+                return ops.resample_image(t.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full)
         cfg = self._cfg_head_i420.get(key)
         if cfg is None:
             cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)

@@ -1146,3 +1146,66 @@ def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False)
     L.check(L.lib().fsr_i420_to_image(_p(frames), _p(img), n, h, w, CHROMA_SITINGS[siting], yuv_matrix_code(matrix), int(bool(full_range)),
                                       _stream()), "fsr_i420_to_image")
     return img.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------------- arbitrary output size
+_aa_taps_cache = {}   # (in_size, out_size, device) -> (weights (out, k) float32, start (out,) int32, count (out,) int32, k)
+RESAMPLE_KINDS = {"f32": L.OUT_F32, "u8": L.OUT_U8, "i420": L.OUT_I420}
+
+
+def aa_taps(in_size, out_size, device):
+    """Device tensors of dataloader.aa_bicubic_taps(in_size, out_size): the normalised float32 taps of the antialiased bicubic
+    (torch's upsample_bicubic2d_aa) of one axis, in either direction.  Cached per (in, out, device); a table is built and
+    uploaded on first use, which must lie OUTSIDE graph capture (InferencePipeline's warm-up call sees to it)."""
+    from .dataloader import aa_bicubic_taps
+    key = (int(in_size), int(out_size), str(torch.device(device)))
+    hit = _aa_taps_cache.get(key)
+    if hit is None:
+        if key[0] <= 0 or key[1] <= 0:
+            raise ValueError("aa_taps needs positive sizes, got %d -> %d" % key[:2])
+        start, count, w, k = aa_bicubic_taps(key[0], key[1])
+        hit = _aa_taps_cache[key] = (torch.from_numpy(w).to(device), torch.from_numpy(start).to(device),
+                                     torch.from_numpy(count).to(device), int(k))
+    return hit
+
+
+def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=False):
+    """Antialiased bicubic resize of a head output to out_h x out_w, fused with the output conversion (fsr_resample_image;
+    DESIGN.md §6d).  t_nhwc: contiguous float32 (N,H,W,3) tanh output (the NHWC buffer behind Generator.forward's view).
+      kind "f32" : float32 (N,3,out_h,out_w) VIEW of an NHWC buffer, 2 v - 1 of the resized c = (t + 1) / 2 -- what
+                   F.interpolate(t, mode="bicubic", antialias=True, align_corners=False) returns;
+      kind "u8"  : uint8 (N,out_h,out_w,3), (unsigned char)(clamp(v, 0, 1) * 255): forward_u8's bytes at another size;
+      kind "i420": uint8 (N, i420_frame_bytes(out_h, out_w)), the I420 planes of clamp(v, 0, 1) in (matrix, full_range); even extents."""
+    _check_dev(t_nhwc)
+    if kind not in RESAMPLE_KINDS:
+        raise ValueError("resample_image kind must be one of %s, got %r" % (sorted(RESAMPLE_KINDS), kind))
+    if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
+        raise ValueError("resample_image expects a contiguous float32 (N,H,W,3) tensor, got %s %s" % (t_nhwc.dtype, tuple(t_nhwc.shape)))
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h <= 0 or out_w <= 0:
+        raise ValueError("resample_image needs a positive output size, got %d x %d" % (out_h, out_w))
+    mcode = yuv_matrix_code(matrix) if kind == "i420" else 0
+    if kind == "i420" and (out_h % 2 or out_w % 2):
+        raise ValueError("I420 output needs even output extents, got %d x %d" % (out_h, out_w))
+    n, h, w, _ = t_nhwc.shape
+    wy, ymin, ysize, ky = aa_taps(h, out_h, t_nhwc.device)
+    wx, xmin, xsize, kx = aa_taps(w, out_w, t_nhwc.device)
+    if kind == "f32":
+        out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=t_nhwc.device)
+    elif kind == "u8":
+        out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=t_nhwc.device)
+    else:
+        out = torch.empty((n, i420_frame_bytes(out_h, out_w)), dtype=torch.uint8, device=t_nhwc.device)
+    prof = PROFILE_RESAMPLE
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    L.check(L.lib().fsr_resample_image(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx,
+                                       RESAMPLE_KINDS[kind], mcode, int(bool(full_range)), _p(out), _stream()), "fsr_resample_image")
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, t_nhwc.numel() * 4 + out.numel() * out.element_size()))
+    return out.permute(0, 3, 1, 2) if kind == "f32" else out
+
+
+PROFILE_RESAMPLE = None   # a list: every resample_image launch appends (start event, end event, algorithmic bytes) -- tools/video_bench.py

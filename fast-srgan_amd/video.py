@@ -7,6 +7,10 @@ library is involved.  Frames stay planar YUV 4:2:0 end to end: the device conver
 RGB (fsr_i420_to_image) and the head's epilogue stores finished I420 planes (FSR_OUT_I420), so the host only moves bytes
 -- 1.5 per output pixel instead of 3.  The colour contract (matrices, ranges, chroma siting) is DESIGN.md §6c.
 
+`--size WxH` (exact, both even) or `--scale S` (relative to the input, rounded to even numbers) pick the output size -- 640x360 to
+1080p is `--size 1920x1080` or `--scale 3`; the default is the network's 4x.  The resize is the antialiased bicubic fused with the
+I420 encode after the head, inside the same graph replay.
+
 Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
 stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
 device batch at a time: a stream of any length passes through a pipe.
@@ -137,6 +141,9 @@ parser.add_argument("--matrix", default="bt601", choices=MATRICES, help="colour 
 parser.add_argument("--range", default="limited", choices=["limited", "full"], help="input range (XCOLORRANGE overrides it)")
 parser.add_argument("--out_matrix", default=None, choices=MATRICES, help="colour matrix of the output (default: the input's)")
 parser.add_argument("--out_range", default=None, choices=["limited", "full"], help="output range (default: the input's)")
+_size_flags = parser.add_mutually_exclusive_group()
+_size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="exact output size, both even (default: 4x the input)")
+_size_flags.add_argument("--scale", default=None, type=float, help="output size relative to the INPUT, rounded to even numbers")
 
 
 def _status(msg):
@@ -147,8 +154,12 @@ def main(argv=None):
     import torch
 
     from .config import load_config
-    from .inference import InferencePipeline, load_generator
+    from .inference import InferencePipeline, load_generator, resolve_out_size
     args = parser.parse_args(argv)
+    try:
+        resolve_out_size(2, 2, args.size, args.scale, even=True)      # a malformed or odd --size fails before the stream is opened
+    except ValueError as exc:
+        raise SystemExit("video: %s" % exc)
     if not torch.cuda.is_available():
         raise SystemExit("fast-srgan_amd runs on an MI355X only: no GPU is visible")
     fin = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
@@ -162,13 +173,16 @@ def main(argv=None):
         model = load_generator(config, "models/model.pt", "cuda", args.compute_dtype)
         s = 2 ** len(model.upsampling)
         h, w = reader.height, reader.width
-        _status("video: %dx%d -> %dx%d, %s %s -> %s %s, chroma siting %s" % (
-            w, h, s * w, s * h, args.matrix, "full" if full else "limited", out_matrix, "full" if out_full else "limited", reader.siting))
-        writer = Y4MWriter(fout, s * w, s * h, reader.frame_rate, reader.aspect, reader.interlace, out_full)
+        out_size = resolve_out_size(h, w, args.size, args.scale, even=True)
+        oh, ow = out_size or (s * h, s * w)
+        _status("video: %dx%d -> %dx%d%s, %s %s -> %s %s, chroma siting %s" % (
+            w, h, ow, oh, "" if out_size is None else " (network %dx%d, resized)" % (s * w, s * h),
+            args.matrix, "full" if full else "limited", out_matrix, "full" if out_full else "limited", reader.siting))
+        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full)
         pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False)
         n, t0, t1 = 0, time.perf_counter(), None
         for y in pipe.run_yuv420(reader.frames(), h, w, siting=reader.siting, matrix=args.matrix, full_range=full,
-                                 out_matrix=out_matrix, out_full_range=out_full):
+                                 out_matrix=out_matrix, out_full_range=out_full, out_size=out_size):
             writer.write_frame(y)       # (a view of the pinned result buffer: written before the slot is reused)
             n += 1
             if n == args.batch:

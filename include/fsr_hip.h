@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 11
+#define FSR_ABI_VERSION 12
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
@@ -243,6 +243,23 @@ int fsr_u8_to_image(const uint8_t* frames, float* img, long long count, fsr_stre
  * FSR_YUV_BT601 / FSR_YUV_BT709, full_range 0 / 1. */
 int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
                       fsr_stream_t stream);
+
+/* ------------------------------------------------------------------ arbitrary output size: antialiased bicubic resize of the head output
+ * t: the head's float tanh output [n,h,w,3] (FSR_OUT_F32 of any dtype's head) -> an oh x ow image in ONE fused kernel (horizontal pass
+ * of a tile's source-row window into LDS, vertical pass from LDS, conversion, store; no global intermediate, no atomics).  The
+ * arithmetic is torch's upsample_bicubic2d_aa (F.interpolate(mode="bicubic", antialias=True, align_corners=False)) on c = (t + 1) / 2:
+ *   v[yo][xo][ch] = sum_j wy[yo][j] * (sum_k wx[xo][k] * c[ymin[yo] + j][xmin[xo] + k][ch])      (float32, horizontal sum first)
+ * wy float [oh][ky], ymin / ysize int [oh] and wx float [ow][kx], xmin / xsize int [ow] are the normalised tap tables of the two axes
+ * (cubic a = -0.5; support 2 * max(in / out, 1); the tables of fsr_crop_resize, for any ratio in either direction).
+ * out_kind: FSR_OUT_F32  float [n,oh,ow,3] = 2 v - 1, unclamped;
+ *           FSR_OUT_U8   uint8 [n,oh,ow,3] = (unsigned char)(clamp(v, 0, 1) * 255) -- the truncating cast of fsr_conv3x3's FSR_OUT_U8, so
+ *                        identity taps reproduce its bytes;
+ *           FSR_OUT_I420 [n][oh * ow * 3 / 2] I420 payloads of clamp(v, 0, 1) (oh, ow even): Y per pixel, Cb / Cr the mean of E_C over each
+ *                        2x2 block, C420jpeg siting, yuv_matrix / yuv_full_range as in fsr_conv_desc.
+ * Any up-scaling factor; down-scaling up to h / oh <= 8 and w / ow <= 8 (ky, kx <= 33).  n * oh * ow and h * w stay below 2^31. */
+int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
+                       const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int yuv_matrix, int yuv_full_range,
+                       void* out, fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ first-layer convolutions straight from the image
  * Conv2d(3 -> cout, k3, p1) of Generator.neck (model.py:75-78), Discriminator.neck (model.py:143-146) and

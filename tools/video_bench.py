@@ -7,7 +7,15 @@
      (f16, --batch 32), run as a child process: its own steady-state figure (frames after the first batch, whose plan build and
      graph capture it excludes) and the wall time of the whole process.
 
+  3. `--resize`: the arbitrary-output-size leg alone.  360x640,
+     batch 8, f16, every path one hipGraph, device events, interleaved round by round:
+       (a) forward_u8 at the native 1440x2560;   (b) forward_u8(out_size=(1080, 1920)), the fused resize after the head;
+       (c) the same frames composed in torch from the float head: F.interpolate(bicubic, antialias=True), clamp, x255, uint8, permute;
+     then (a) and (b) again for forward_yuv420, and the resample kernel alone from its own events (ops.PROFILE_RESAMPLE) with its
+     achieved bytes/s over its algorithmic bytes: 12 B per source pixel + 3 (RGB) or 1.5 (I420) B per output pixel.
+
     python tools/video_bench.py [--frames 2048] [--rounds 7] [--replays 20] [--modes f16,x3]
+    python tools/video_bench.py --resize [--rounds 7] [--replays 20]
 """
 import argparse
 import importlib
@@ -87,6 +95,65 @@ def model_only(sd, mode, rounds, replays):
     return fps_rgb, fps_yuv
 
 
+def resize_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, size=(1080, 1920)):
+    import torch.nn.functional as F
+    dev = "cuda:0"
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+    x_rgb = torch.from_numpy(rng.integers(0, 256, size=(b, h, w, 3), dtype=np.uint8)).to(dev)
+    x_yuv = torch.from_numpy(rng.integers(0, 256, size=(b, ops.i420_frame_bytes(h, w)), dtype=np.uint8)).to(dev)
+
+    def torch_path(x):
+        with torch.no_grad():
+            t = G(ops.u8_to_image(x))
+            y = F.interpolate(t, size=size, mode="bicubic", antialias=True, align_corners=False)
+            return (((y + 1) / 2).clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+    # the three paths agree before anything is timed (codes within 1: float32 resizes of one head output in two summation orders)
+    y_b, y_c = G.forward_u8(x_rgb, out_size=size), torch_path(x_rgb)
+    diff = (y_b.int() - y_c.int()).abs()
+    print("resize      fused vs torch-composed uint8 frames: max |code difference| %d, %.4f %% of the samples differ"
+          % (int(diff.max()), 100.0 * float((diff > 0).float().mean())), flush=True)
+    paths = [("u8 native %dx%d" % (4 * h, 4 * w), graphed(G.forward_u8, x_rgb)),
+             ("u8 fused resize %dx%d" % size, graphed(lambda x: G.forward_u8(x, out_size=size), x_rgb)),
+             ("u8 torch-composed resize", graphed(torch_path, x_rgb)),
+             ("yuv420 native", graphed(lambda x: G.forward_yuv420(x, h, w), x_yuv)),
+             ("yuv420 fused resize", graphed(lambda x: G.forward_yuv420(x, h, w, out_size=size), x_yuv))]
+    times = [[] for _ in paths]
+    for _, g in paths:
+        time_graph(g, 3)
+    for r in range(rounds):
+        order = list(range(len(paths)))
+        for i in (order if r % 2 == 0 else order[::-1]):
+            times[i].append(time_graph(paths[i][1], replays))
+    med = [statistics.median(t) for t in times]
+    for (name, _), m, t in zip(paths, med, times):
+        print("resize      %-4s batch %d %dx%d  %-28s %7.3f ms/batch  %7.1f FPS   [per-round ms %s]" % (
+            mode, b, h, w, name, 1e3 * m, b / m, " ".join("%.3f" % (1e3 * v) for v in t)), flush=True)
+    print("resize      fused / torch-composed (u8): %.3f x faster;  fused resize - native: u8 %+.3f ms, yuv420 %+.3f ms per batch"
+          % (med[2] / med[1], 1e3 * (med[1] - med[0]), 1e3 * (med[4] - med[3])), flush=True)
+    # the kernel alone, from its own events, on a real head output
+    with torch.no_grad():
+        t = G(ops.u8_to_image(x_rgb)).permute(0, 2, 3, 1)
+    for kind in ("u8", "i420"):
+        for _ in range(5):
+            ops.resample_image(t, size[0], size[1], kind)
+        torch.cuda.synchronize()
+        ops.PROFILE_RESAMPLE = []
+        for _ in range(50):
+            ops.resample_image(t, size[0], size[1], kind)
+        torch.cuda.synchronize()
+        prof, ops.PROFILE_RESAMPLE = ops.PROFILE_RESAMPLE, None
+        ms = sorted(e0.elapsed_time(e1) for e0, e1, _ in prof)
+        nbytes = prof[0][2]
+        print("resize      kernel resample_kernel<%s,9> %dx%d -> %dx%d batch %d: median %.1f us, min %.1f us (own events, 50 launches); "
+              "%.1f MB algorithmic -> %.2f TB/s at the median" % (kind, h * 4, w * 4, size[0], size[1], b, 1e3 * ms[len(ms) // 2], 1e3 * ms[0],
+                                                               nbytes / 1e6, nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
+    return med
+
+
 def end_to_end(sd, frames, mode):
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "configs"))
@@ -123,11 +190,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--modes", default="f16,x3")
+    ap.add_argument("--resize", action="store_true", help="run the arbitrary-output-size leg only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("video_bench needs the MI355X")
     sd = shipped_state_dict()
     print("device:", torch.cuda.get_device_name(0), flush=True)
+    if args.resize:
+        resize_leg(sd, args.rounds, args.replays)
+        return
     model = {}
     for mode in args.modes.split(","):
         model[mode] = model_only(sd, mode, args.rounds, args.replays)
