@@ -20,7 +20,7 @@ OUT_DTYPE, OUT_F32, OUT_U8, OUT_I420 = 0, 1, 2, 3
 YUV_BT601, YUV_BT709 = 0, 1                 # fsr_conv_desc.yuv_matrix, fsr_i420_to_image
 SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_image's input
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
@@ -74,6 +74,9 @@ SIGNATURES = {
                                   c_float, c_float, c_float, P, c_int, P]),
     "fsr_u8_to_image": (c_int, [P, P, c_ll, P]),
     "fsr_i420_to_image": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "fsr_i420_to_image_deep": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "fsr_image_to_i420": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_resample_image_i420_deep": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "fsr_resample_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "fsr_pack_conv3x3_c3": (c_int, [c_int, P, c_int, P, c_int, P]),
     "fsr_tanh_bwd_image": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, c_int, P, P, P, P]),

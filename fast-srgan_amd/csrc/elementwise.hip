@@ -419,18 +419,25 @@ __global__ __launch_bounds__(256) void u8_to_image_kernel(const unsigned char* _
 // "Video"): one thread per pixel, chroma upsampled bilinearly with edge clamp at the declared siting -- luma pixel (y, x) reads
 // chroma at ((y - 1/2) / 2, (x - 1/2) / 2) (C420jpeg) or ((y - 1/2) / 2, x / 2) (C420mpeg2); then the inverse of the encode
 // matrix, R, G, B clamped to [0, 1] (no 8-bit RGB in between).
-__global__ __launch_bounds__(256) void i420_to_image_kernel(const unsigned char* __restrict__ src, float* __restrict__ dst, int n, int h,
-                                                            int w, int mpeg2, int matrix, int full) {
+// S: the sample type -- unsigned char, or unsigned short for the 9..16-bit payloads of fsr_i420_to_image_deep (little-endian, the
+// value in the low `depth` bits; a stored value above 2^depth - 1 is taken as it is, the clamp of R, G, B deals with it).  The
+// coefficients scale with the depth: limited Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8); full Y = (2^d - 1) E_Y,
+// C = 2^(d-1) + (2^d - 1) E_C -- for S = unsigned char d is the constant 8.
+template <typename S>
+__global__ __launch_bounds__(256) void i420_to_image_kernel(const S* __restrict__ src, float* __restrict__ dst, int n, int h,
+                                                            int w, int mpeg2, int matrix, int full, int depth) {
+  const int d = sizeof(S) == 1 ? 8 : depth;
   const int ch = (h + 1) >> 1, cw = (w + 1) >> 1;
-  const long long plane = (long long)h * w, cplane = (long long)ch * cw, fbytes = plane + 2 * cplane;
+  const long long plane = (long long)h * w, cplane = (long long)ch * cw, fbytes = plane + 2 * cplane;   // (samples)
   const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
   const float kg = 1.f - kr - kb;
-  const float ys = full ? 255.f : 219.f, yo = full ? 0.f : 16.f, cs = full ? 255.f : 224.f;
+  const float up = (float)(1 << (d - 8)), top = (float)((1 << d) - 1), co = 128.f * up;
+  const float ys = full ? top : 219.f * up, yo = full ? 0.f : 16.f * up, cs = full ? top : 224.f * up;
   const long long total = (long long)n * plane;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const long long img = i / plane;
     const int p = (int)(i - img * plane), y = p / w, x = p - y * w;
-    const unsigned char* f = src + img * fbytes;
+    const S* f = src + img * fbytes;
     const float cy = 0.5f * (float)y - 0.25f, cx = mpeg2 ? 0.5f * (float)x : 0.5f * (float)x - 0.25f;
     const float fy0 = floorf(cy), fx0 = floorf(cx);
     const float fy = cy - fy0, fx = cx - fx0;
@@ -439,18 +446,60 @@ __global__ __launch_bounds__(256) void i420_to_image_kernel(const unsigned char*
     float c[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const unsigned char* q = f + plane + k * cplane;
+      const S* q = f + plane + k * cplane;
       const float top = (1.f - fx) * (float)q[y0 * cw + x0] + fx * (float)q[y0 * cw + x1];
       const float bot = (1.f - fx) * (float)q[y1 * cw + x0] + fx * (float)q[y1 * cw + x1];
       c[k] = (1.f - fy) * top + fy * bot;
     }
-    const float ey = ((float)f[p] - yo) / ys, ecb = (c[0] - 128.f) / cs, ecr = (c[1] - 128.f) / cs;
+    const float ey = ((float)f[p] - yo) / ys, ecb = (c[0] - co) / cs, ecr = (c[1] - co) / cs;
     const float r = ey + 2.f * (1.f - kr) * ecr, b = ey + 2.f * (1.f - kb) * ecb;
     const float g = (ey - kr * r - kb * b) / kg;
     float* o = dst + i * 3;
     o[0] = 2.f * fminf(fmaxf(r, 0.f), 1.f) - 1.f;
     o[1] = 2.f * fminf(fmaxf(g, 0.f), 1.f) - 1.f;
     o[2] = 2.f * fminf(fmaxf(b, 0.f), 1.f) - 1.f;
+  }
+}
+
+// float tanh output t [n,h,w,3] -> I420 planes (fsr_image_to_i420; the encode of DESIGN.md §6c at any depth 8..16, what the head's
+// FSR_OUT_I420 epilogue computes for 8 bits): a streaming kernel in the shape of the resampler's I420 stage.  A thread owns 4 columns x
+// 2 rows -- two whole 2x2 blocks, so no LDS, no shuffle, no atomics: three 16-byte loads per row (the rows are only 8-byte aligned when
+// w is not a multiple of 4; 6 floats per row in the last unit of such a row), c = clamp((t + 1) / 2, 0, 1), then i420_store_2x4: one
+// 4- or 8-byte Y store per row and 2 + 2 chroma samples.  Grid-stride over the n * (h / 2) * ceil(w / 4) units (< 2^31: host checked).
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <typename C>
+__global__ __launch_bounds__(256) void image_to_i420_kernel(const float* __restrict__ t, C* __restrict__ out, int n, int h, int w, int matrix,
+                                                            int full, int depth) {
+  const i420_coef kc = i420_coefs(matrix, full, sizeof(C) == 1 ? 8 : depth);
+  const unsigned wq = (unsigned)(w + 3) >> 2, hp = (unsigned)h >> 1;
+  const unsigned units = (unsigned)n * hp * wq;
+  const size_t fsamples = (size_t)h * w + 2 * ((size_t)(h >> 1) * (size_t)(w >> 1));
+  for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < units; u += gridDim.x * 256u) {
+    const unsigned row = u / wq, xq = u - row * wq;
+    const unsigned img = row / hp, yp = row - img * hp;
+    const int x = (int)xq * 4, y = (int)yp * 2;
+    const int cnt = w - x < 4 ? w - x : 4;       // 2 or 4: w is even
+    float v[2][12];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      const float* p = t + (((size_t)img * h + (y + m)) * w + x) * 3;
+      f32x4_a4 q0 = *(const f32x4_a4*)p, q1, q2 = {0.f, 0.f, 0.f, 0.f};
+      if (cnt == 4) {
+        q1 = *(const f32x4_a4*)(p + 4);
+        q2 = *(const f32x4_a4*)(p + 8);
+      } else {
+        const f32x2_a4 e = *(const f32x2_a4*)(p + 4);
+        q1 = (f32x4_a4){e[0], e[1], 0.f, 0.f};
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[m][k] = fminf(fmaxf((q0[k] + 1.f) / 2.f, 0.f), 1.f);
+        v[m][4 + k] = fminf(fmaxf((q1[k] + 1.f) / 2.f, 0.f), 1.f);
+        v[m][8 + k] = fminf(fmaxf((q2[k] + 1.f) / 2.f, 0.f), 1.f);
+      }
+    }
+    i420_store_2x4<C>(kc, v, out + (size_t)img * fsamples, h, w, y, x, cnt);
   }
 }
 
@@ -786,18 +835,63 @@ extern "C" int fsr_u8_to_image(const uint8_t* frames, float* img, long long coun
   return fsr_check_launch("u8_to_image_kernel");
 }
 
-extern "C" int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
-                                 fsr_stream_t stream_) {
-  if (!frames || !img || n <= 0 || h <= 0 || w <= 0) return fsr_fail(-1, "fsr_i420_to_image: bad argument");
+namespace {
+int i420_to_image_launch(const char* who, const void* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
+                         int depth, fsr_stream_t stream_) {
+  if (!frames || !img || n <= 0 || h <= 0 || w <= 0) return fsr_fail(-1, "%s: bad argument", who);
   if ((siting != FSR_SITING_JPEG && siting != FSR_SITING_MPEG2) || (matrix != FSR_YUV_BT601 && matrix != FSR_YUV_BT709) ||
       (full_range != 0 && full_range != 1))
-    return fsr_fail(-2, "fsr_i420_to_image: unknown siting %d / matrix %d / range %d", siting, matrix, full_range);
-  if ((long long)h * w >= (1LL << 31)) return fsr_fail(-2, "fsr_i420_to_image: frames of 2^31 or more pixels are not supported");
+    return fsr_fail(-2, "%s: unknown siting %d / matrix %d / range %d", who, siting, matrix, full_range);
+  if ((long long)h * w >= (1LL << 31)) return fsr_fail(-2, "%s: frames of 2^31 or more pixels are not supported", who);
   long long blocks = ((long long)n * h * w + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(i420_to_image_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, frames, img, n, h, w,
-                     siting == FSR_SITING_MPEG2 ? 1 : 0, matrix, full_range);
-  return fsr_check_launch("i420_to_image_kernel");
+  const int mpeg2 = siting == FSR_SITING_MPEG2 ? 1 : 0;
+  if (depth == 8) {
+    hipLaunchKernelGGL(i420_to_image_kernel<unsigned char>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_,
+                       (const unsigned char*)frames, img, n, h, w, mpeg2, matrix, full_range, 8);
+    return fsr_check_launch("i420_to_image_kernel");
+  }
+  hipLaunchKernelGGL(i420_to_image_kernel<unsigned short>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_,
+                     (const unsigned short*)frames, img, n, h, w, mpeg2, matrix, full_range, depth);
+  fsr_note_kernel("i420_to_image_kernel<%s>", "u16");
+  return fsr_check_launch("i420_to_image_kernel<u16>");
+}
+}  // namespace
+
+extern "C" int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
+                                 fsr_stream_t stream_) {
+  return i420_to_image_launch("fsr_i420_to_image", frames, img, n, h, w, siting, matrix, full_range, 8, stream_);
+}
+
+extern "C" int fsr_i420_to_image_deep(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
+                                      int depth, fsr_stream_t stream_) {
+  if (depth < 9 || depth > 16) return fsr_fail(-2, "fsr_i420_to_image_deep: depth %d is outside 9..16", depth);
+  if (((size_t)frames & 1) != 0) return fsr_fail(-2, "fsr_i420_to_image_deep: the payloads of 16-bit samples must be 2-byte aligned");
+  return i420_to_image_launch("fsr_i420_to_image_deep", frames, img, n, h, w, siting, matrix, full_range, depth, stream_);
+}
+
+extern "C" int fsr_image_to_i420(const float* t, int n, int h, int w, int matrix, int full_range, int depth, void* out,
+                                 fsr_stream_t stream_) {
+  if (!t || !out) return fsr_fail(-1, "fsr_image_to_i420: null argument");
+  if (n <= 0 || h <= 0 || w <= 0) return fsr_fail(-2, "fsr_image_to_i420: bad sizes (n %d, %d x %d)", n, h, w);
+  if ((h & 1) || (w & 1)) return fsr_fail(-2, "fsr_image_to_i420: I420 output needs even output extents (%d x %d)", h, w);
+  if ((matrix != FSR_YUV_BT601 && matrix != FSR_YUV_BT709) || (full_range != 0 && full_range != 1))
+    return fsr_fail(-2, "fsr_image_to_i420: unknown colour matrix %d / range %d", matrix, full_range);
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_image_to_i420: depth %d is outside 8..16", depth);
+  if ((long long)h * w >= (1LL << 31) || (long long)n * h * w >= (1LL << 31))
+    return fsr_fail(-2, "fsr_image_to_i420: frames of 2^31 or more pixels are not supported");
+  if (((size_t)t & 3) != 0 || (depth > 8 && ((size_t)out & 1) != 0)) return fsr_fail(-2, "fsr_image_to_i420: misaligned tensor");
+  const long long units = (long long)n * (h / 2) * ((w + 3) / 4);
+  long long blocks = (units + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (depth == 8)
+    hipLaunchKernelGGL(image_to_i420_kernel<unsigned char>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, t,
+                       (unsigned char*)out, n, h, w, matrix, full_range, 8);
+  else
+    hipLaunchKernelGGL(image_to_i420_kernel<unsigned short>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, t,
+                       (unsigned short*)out, n, h, w, matrix, full_range, depth);
+  fsr_note_kernel("image_to_i420_kernel<%s>", depth == 8 ? "u8" : "u16");
+  return fsr_check_launch("image_to_i420_kernel");
 }
 
 extern "C" size_t fsr_tanh_bwd_scratch(void) { return (size_t)512 * 64 * 3 * sizeof(float); }

@@ -303,28 +303,36 @@ __device__ __forceinline__ unsigned char image_u8(float y) {
 // Out: the two pixels' Y codes, and the block's Cb / Cr codes -- the mean of E_C over the block, C420jpeg siting -- in both lanes.
 //   c = clamp((t + 1) / 2, 0, 1);  E_Y = Kr R + Kg G + Kb B;  E_Cb = (B - E_Y) / (2 (1 - Kb));  E_Cr = (R - E_Y) / (2 (1 - Kr))
 //   limited: Y = 16 + 219 E_Y, C = 128 + 224 E_C;  full: Y = 255 E_Y, C = 128 + 255 E_C;  code = clamp(floor(v + 0.5), 0, 255)
-__device__ __forceinline__ unsigned char yuv_code(float v) { return (unsigned char)fminf(fmaxf(floorf(v + 0.5f), 0.f), 255.f); }
+// Deeper samples (9..16 bits, fsr_image_to_i420 and the 16-bit form of the resampler's I420 stage) use the same helpers with the
+// depth's coefficients and a 16-bit code type C:  limited Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8);
+// full Y = (2^d - 1) E_Y, C = 2^(d-1) + (2^d - 1) E_C;  code = clamp(floor(v + 0.5), 0, 2^d - 1).  depth = 8 (the default, a
+// constant in the head kernels) gives the numbers above.
+template <typename C = unsigned char>
+__device__ __forceinline__ C yuv_code(float v, float cmax = 255.f) { return (C)fminf(fmaxf(floorf(v + 0.5f), 0.f), cmax); }
 // The per-pixel and per-block parts, shared with the resampler (resample.hip), whose threads hold whole 2x2 blocks:
 //   i420_pixel : clamped (R, G, B) in [0, 1] -> the pixel's Y code; db = B - E_Y, dr = R - E_Y
 //   i420_chroma: the sums of db and dr over the four pixels of a block (the vertical pair first, then the two columns) -> Cb, Cr codes
 struct i420_coef {
-  float kr, kg, kb, ys, yo, cs;
+  float kr, kg, kb, ys, yo, cs, co, cmax;
 };
-__device__ __forceinline__ i420_coef i420_coefs(int matrix, int full) {
+__device__ __forceinline__ i420_coef i420_coefs(int matrix, int full, int depth = 8) {
   const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
   const float kg = 1.f - kr - kb;
-  const float ys = full ? 255.f : 219.f, yo = full ? 0.f : 16.f, cs = full ? 255.f : 224.f;
-  return i420_coef{kr, kg, kb, ys, yo, cs};
+  const float up = (float)(1 << (depth - 8)), top = (float)((1 << depth) - 1);   // exact: depth <= 16
+  const float ys = full ? top : 219.f * up, yo = full ? 0.f : 16.f * up, cs = full ? top : 224.f * up;
+  return i420_coef{kr, kg, kb, ys, yo, cs, 128.f * up, top};
 }
-__device__ __forceinline__ unsigned char i420_pixel(const i420_coef& k, float r, float g, float b, float& db, float& dr) {
+template <typename C = unsigned char>
+__device__ __forceinline__ C i420_pixel(const i420_coef& k, float r, float g, float b, float& db, float& dr) {
   const float ey = k.kr * r + k.kg * g + k.kb * b;
   db = b - ey;
   dr = r - ey;
-  return yuv_code(k.yo + k.ys * ey);
+  return yuv_code<C>(k.yo + k.ys * ey, k.cmax);
 }
-__device__ __forceinline__ void i420_chroma(const i420_coef& k, float sb, float sr, unsigned char& cb, unsigned char& cr) {
-  cb = yuv_code(128.f + k.cs * (sb * 0.25f / (2.f * (1.f - k.kb))));
-  cr = yuv_code(128.f + k.cs * (sr * 0.25f / (2.f * (1.f - k.kr))));
+template <typename C>
+__device__ __forceinline__ void i420_chroma(const i420_coef& k, float sb, float sr, C& cb, C& cr) {
+  cb = yuv_code<C>(k.co + k.cs * (sb * 0.25f / (2.f * (1.f - k.kb))), k.cmax);
+  cr = yuv_code<C>(k.co + k.cs * (sr * 0.25f / (2.f * (1.f - k.kr))), k.cmax);
 }
 __device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, int full, unsigned char (&y)[2], unsigned char& cb,
                                           unsigned char& cr) {
@@ -343,6 +351,66 @@ __device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, in
   sb += __shfl_xor(sb, 1, 64);
   sr += __shfl_xor(sr, 1, 64);
   i420_chroma(k, sb, sr, cb, cr);
+}
+
+// ---- I420 planes from a thread that holds 4 columns x 2 rows -- two whole 2x2 blocks, no shuffle (the resampler's I420 stage and
+// fsr_image_to_i420).  C = unsigned char (8-bit samples) or unsigned short (9..16 bits, little-endian, the value in the low bits).
+// `count` (1..4) codes b[0..count) to p: one 4 * sizeof(C)-byte store, halves of it or single codes, whatever p's alignment allows
+template <typename C>
+__device__ __forceinline__ void store_codes4(C* p, const C (&b)[4], int count) {
+  constexpr int S = 8 * (int)sizeof(C);
+  typedef typename std::conditional<sizeof(C) == 1, unsigned short, unsigned>::type pair_t;
+  const size_t ad = (size_t)p;
+  const pair_t lo = (pair_t)((pair_t)b[0] | ((pair_t)b[1] << S)), hi = (pair_t)((pair_t)b[2] | ((pair_t)b[3] << S));
+  if (count == 4 && (ad & (4 * sizeof(C) - 1)) == 0) {
+    if constexpr (sizeof(C) == 1) *(unsigned*)p = (unsigned)lo | ((unsigned)hi << 16);
+    else *(u32x2*)p = (u32x2){lo, hi};
+  } else if ((ad & (2 * sizeof(C) - 1)) == 0 && (count & 1) == 0) {
+    *(pair_t*)p = lo;
+    if (count == 4) *(pair_t*)(p + 2) = hi;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i < count) p[i] = b[i];
+  }
+}
+// v[m][3 c + ch]: clamped (R, G, B) in [0, 1] of row yo + m, column xg + c of a frame of oh x ow (both even; yo, xg even); cnt = 2 or 4
+// valid columns.  Per column the vertical pair first, then the two columns of a block (i420_quad's order of the chroma sum).
+template <typename C>
+__device__ __forceinline__ void i420_store_2x4(const i420_coef& kc, const float (&v)[2][12], C* frame, int oh, int ow, int yo, int xg,
+                                               int cnt) {
+  const size_t plane = (size_t)oh * ow, cw = (size_t)(ow >> 1), cplane = (size_t)(oh >> 1) * cw;
+  C yv[2][4], cb[2], cr[2];
+  float sb[4], sr[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    sb[c] = 0.f;
+    sr[c] = 0.f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      float db, dr;
+      yv[m][c] = i420_pixel<C>(kc, v[m][3 * c], v[m][3 * c + 1], v[m][3 * c + 2], db, dr);
+      sb[c] += db;
+      sr[c] += dr;
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) i420_chroma(kc, sb[2 * p] + sb[2 * p + 1], sr[2 * p] + sr[2 * p + 1], cb[p], cr[p]);
+  store_codes4(frame + (size_t)yo * ow + xg, yv[0], cnt);
+  store_codes4(frame + (size_t)(yo + 1) * ow + xg, yv[1], cnt);
+  C* c0 = frame + plane + (size_t)(yo >> 1) * cw + (xg >> 1);
+  if (cnt == 4 && ((size_t)c0 & (2 * sizeof(C) - 1)) == 0 && (cplane & 1) == 0) {
+    typedef typename std::conditional<sizeof(C) == 1, unsigned short, unsigned>::type pair_t;
+    *(pair_t*)c0 = (pair_t)((pair_t)cb[0] | ((pair_t)cb[1] << (8 * sizeof(C))));
+    *(pair_t*)(c0 + cplane) = (pair_t)((pair_t)cr[0] | ((pair_t)cr[1] << (8 * sizeof(C))));
+  } else {
+    c0[0] = cb[0];
+    c0[cplane] = cr[0];
+    if (cnt == 4) {
+      c0[1] = cb[1];
+      c0[cplane + 1] = cr[1];
+    }
+  }
 }
 
 // sum over the 64 lanes of a wave; every lane gets the total

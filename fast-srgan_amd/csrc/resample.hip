@@ -12,7 +12,8 @@
 //      (rows of up to 5 or 9 taps: up-scales, down-scales up to 2) and walks the source rows [r0, r1) of the tile's window: lds[row][e] = sum_k wx[k] * c[row][xmin + k];
 //   2. vertical pass from LDS: a thread takes 4 consecutive floats of an output row (one ds_read_b128 per tap, the row and its
 //      taps wave-uniform), converts and stores 16 bytes of floats or one dword of bytes; for I420 it takes 4 columns x 2 rows --
-//      two whole 2x2 blocks, no shuffle -- and stores a dword of Y per row and two bytes of Cb and of Cr.
+//      two whole 2x2 blocks, no shuffle -- and stores a dword of Y per row and two bytes of Cb and of Cr (i420_store_2x4,
+//      fsr_common.h; fsr_resample_image_i420_deep: the same stage with 16-bit samples at depth 9..16, 8 and 4 bytes).
 // Every table value is clamped to the image and to the LDS window before it is used as an index: tables that are not the ones
 // the contract names give wrong pixels, never an access outside the tensors.
 #include "fsr_common.h"
@@ -41,30 +42,17 @@ struct ResampleArgs {
   int rows_cap;           // source rows the LDS allocation holds
   int matrix, full;
   void* out;
+  int depth;              // FSR_OUT_I420 with 16-bit samples: bits per sample (9..16)
 };
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
-// `count` (1..4) bytes b[0..count) to p: one dword, 16-bit halves or single bytes, whatever p's alignment allows
-__device__ __forceinline__ void store_bytes(unsigned char* p, const unsigned char (&b)[4], int count) {
-  const size_t ad = (size_t)p;
-  if (count == 4 && (ad & 3) == 0) {
-    *(unsigned*)p = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
-  } else if ((ad & 1) == 0 && (count & 1) == 0) {
-    *(unsigned short*)p = (unsigned short)(b[0] | (b[1] << 8));
-    if (count == 4) *(unsigned short*)(p + 2) = (unsigned short)(b[2] | (b[3] << 8));
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i < count) p[i] = b[i];
-  }
-}
-
 // KIND: FSR_OUT_F32 / FSR_OUT_U8 / FSR_OUT_I420.  KXS = 5 / 9: rows of at most 5 (every up-scale) / 9 (down-scales up to 2: the
 // network's 4x taken to 3x or 2x of the input) horizontal taps, held in registers; KXS = 0: any tap count, read per use.
-template <int KIND, int KXS>
+// C (FSR_OUT_I420 only): the sample type of the planes -- unsigned char, or unsigned short for 9..16-bit samples (a.depth).
+template <int KIND, int KXS, typename C = unsigned char>
 __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
   HIP_DYNAMIC_SHARED(float, lds)
   int b = blockIdx.x;
@@ -143,13 +131,13 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
         unsigned char by[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) by[i] = (unsigned char)(clamp01(acc[i]) * 255.f);
-        store_bytes((unsigned char*)a.out + o, by, cnt);
+        store_codes4((unsigned char*)a.out + o, by, cnt);
       }
     }
   } else {
-    const i420_coef kc = i420_coefs(a.matrix, a.full);
-    const size_t plane = (size_t)a.oh * a.ow, cw = (size_t)(a.ow >> 1), cplane = (size_t)(a.oh >> 1) * cw;
-    unsigned char* frame = (unsigned char*)a.out + (size_t)n * (plane + 2 * cplane);
+    const i420_coef kc = i420_coefs(a.matrix, a.full, sizeof(C) == 1 ? 8 : a.depth);
+    const size_t plane = (size_t)a.oh * a.ow;
+    C* frame = (C*)a.out + (size_t)n * (plane + 2 * ((size_t)(a.oh >> 1) * (size_t)(a.ow >> 1)));
     const int nitems = (th >> 1) * (RS_TW / 4);
     for (int i = tid; i < nitems; i += 256) {
       const int rp = i / (RS_TW / 4), xl = (i - rp * (RS_TW / 4)) * 4;
@@ -177,39 +165,8 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
           v[m][8 + k] = clamp01(a2[k]);
         }
       }
-      // the lane's columns xl .. xl + 3 are two 2x2 blocks: per column the vertical pair first, then the two columns of a block
-      unsigned char yv[2][4], cb[2], cr[2];
-      float sb[4], sr[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        sb[c] = 0.f;
-        sr[c] = 0.f;
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          float db, dr;
-          yv[m][c] = i420_pixel(kc, v[m][3 * c], v[m][3 * c + 1], v[m][3 * c + 2], db, dr);
-          sb[c] += db;
-          sr[c] += dr;
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < 2; ++p) i420_chroma(kc, sb[2 * p] + sb[2 * p + 1], sr[2 * p] + sr[2 * p + 1], cb[p], cr[p]);
-      const int cnt = imin(4, tw - xl);      // 2 or 4: ow and the tile origin are even
-      const int yo = y0 + 2 * rp, xg = x0 + xl;
-      store_bytes(frame + (size_t)yo * a.ow + xg, yv[0], cnt);
-      store_bytes(frame + (size_t)(yo + 1) * a.ow + xg, yv[1], cnt);
-      unsigned char* c0 = frame + plane + (size_t)(yo >> 1) * cw + (xg >> 1);
-      if (cnt == 4 && ((size_t)c0 & 1) == 0 && (cplane & 1) == 0) {
-        *(unsigned short*)c0 = (unsigned short)(cb[0] | (cb[1] << 8));
-        *(unsigned short*)(c0 + cplane) = (unsigned short)(cr[0] | (cr[1] << 8));
-      } else {
-        c0[0] = cb[0];
-        c0[cplane] = cr[0];
-        if (cnt == 4) {
-          c0[1] = cb[1];
-          c0[cplane + 1] = cr[1];
-        }
-      }
+      // the lane's columns xl .. xl + 3 are two 2x2 blocks; cnt = 2 or 4: ow and the tile origin are even
+      i420_store_2x4<C>(kc, v, frame, a.oh, a.ow, y0 + 2 * rp, x0 + xl, imin(4, tw - xl));
     }
   }
 }
@@ -230,21 +187,20 @@ int window_rows(int in, int out, int th) {
   return rows;
 }
 
-template <int KIND>
+template <int KIND, typename C = unsigned char>
 void launch_kind(const ResampleArgs& a, long long grid, size_t lds_bytes, hipStream_t stream) {
   if (a.kx <= 5)
-    hipLaunchKernelGGL((resample_kernel<KIND, 5>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
+    hipLaunchKernelGGL((resample_kernel<KIND, 5, C>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
   else if (a.kx <= 9)
-    hipLaunchKernelGGL((resample_kernel<KIND, 9>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
+    hipLaunchKernelGGL((resample_kernel<KIND, 9, C>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
   else
-    hipLaunchKernelGGL((resample_kernel<KIND, 0>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
+    hipLaunchKernelGGL((resample_kernel<KIND, 0, C>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
 }
 
-}  // namespace
-
-extern "C" int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin,
-                                  const int* ysize, int ky, const float* wx, const int* xmin, const int* xsize, int kx, int out_kind,
-                                  int yuv_matrix, int yuv_full_range, void* out, fsr_stream_t stream_) {
+// depth: 8, or 9..16 for FSR_OUT_I420 planes of 16-bit samples (fsr_resample_image_i420_deep)
+int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
+                    const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int yuv_matrix, int yuv_full_range, int depth,
+                    void* out, fsr_stream_t stream_) {
   if (!t || !wy || !ymin || !ysize || !wx || !xmin || !xsize || !out) return fsr_fail(-1, "fsr_resample_image: null argument");
   if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ky <= 0 || kx <= 0)
     return fsr_fail(-2, "fsr_resample_image: bad sizes (n %d, %d x %d -> %d x %d, taps %d x %d)", n, h, w, oh, ow, ky, kx);
@@ -278,6 +234,7 @@ extern "C" int fsr_resample_image(const float* t, int n, int h, int w, int oh, i
   a.rows_cap = rows;
   a.matrix = yuv_matrix; a.full = yuv_full_range;
   a.out = out;
+  a.depth = depth;
   const long long grid = (long long)n * a.tiles_x * a.tiles_y;
   if (grid >= (1LL << 31)) return fsr_fail(-2, "fsr_resample_image: too many tiles (%lld)", grid);
   const size_t lds_bytes = (size_t)rows * RS_ROWF * sizeof(float);
@@ -285,7 +242,25 @@ extern "C" int fsr_resample_image(const float* t, int n, int h, int w, int oh, i
   const char* kind = out_kind == FSR_OUT_F32 ? "f32" : (out_kind == FSR_OUT_U8 ? "u8" : "i420");
   if (out_kind == FSR_OUT_F32) launch_kind<FSR_OUT_F32>(a, grid, lds_bytes, stream);
   else if (out_kind == FSR_OUT_U8) launch_kind<FSR_OUT_U8>(a, grid, lds_bytes, stream);
-  else launch_kind<FSR_OUT_I420>(a, grid, lds_bytes, stream);
-  fsr_note_kernel("resample_kernel<%s,%d>", kind, kx <= 5 ? 5 : (kx <= 9 ? 9 : 0));
+  else if (depth == 8) launch_kind<FSR_OUT_I420>(a, grid, lds_bytes, stream);
+  else launch_kind<FSR_OUT_I420, unsigned short>(a, grid, lds_bytes, stream);
+  if (depth == 8) fsr_note_kernel("resample_kernel<%s,%d>", kind, kx <= 5 ? 5 : (kx <= 9 ? 9 : 0));
+  else fsr_note_kernel("resample_kernel<i420,%d,u16>", kx <= 5 ? 5 : (kx <= 9 ? 9 : 0));
   return fsr_check_launch("resample_kernel");
+}
+
+}  // namespace
+
+extern "C" int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin,
+                                  const int* ysize, int ky, const float* wx, const int* xmin, const int* xsize, int kx, int out_kind,
+                                  int yuv_matrix, int yuv_full_range, void* out, fsr_stream_t stream_) {
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, out_kind, yuv_matrix, yuv_full_range, 8, out, stream_);
+}
+
+extern "C" int fsr_resample_image_i420_deep(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin,
+                                            const int* ysize, int ky, const float* wx, const int* xmin, const int* xsize, int kx,
+                                            int yuv_matrix, int yuv_full_range, int depth, void* out, fsr_stream_t stream_) {
+  if (depth < 9 || depth > 16) return fsr_fail(-2, "fsr_resample_image_i420_deep: depth %d is outside 9..16", depth);
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, yuv_matrix, yuv_full_range, depth, out,
+                         stream_);
 }

@@ -16,7 +16,7 @@ import torch
 
 from .config import load_config
 from .model import Generator
-from .ops import i420_frame_bytes
+from .ops import check_depth, i420_frame_bytes
 
 parser = ArgumentParser("Real Time Image Super Resolution")
 parser.add_argument("--image_dir", default=None, required=True, type=str)
@@ -99,7 +99,23 @@ class InferencePipeline:
         self.max_shapes = max(1, int(max_shapes))
         self._plans = {}            # (h, w) -> list of `depth` slots, built lazily (a one-batch bucket only ever builds slot 0)
         self._lru = []              # shapes, least recently used first
-        self._copy_stream = torch.cuda.Stream(device=self.device)
+        self._copy_stream = None    # the D2H stream, created with the first batch
+        self._told = set()          # frame shapes whose reduced batch has been reported
+
+    def _batch_for(self, h, w):
+        """Frames per device batch for h x w inputs: min(batch, Generator.max_batch(h, w)) -- the convolution kernels index tensors
+        below 2^31 elements, and InstanceNorm statistics are per image, so a smaller batch computes the same frames.  A frame
+        that is too large on its own is refused here, before anything is allocated."""
+        limit = self.model.max_batch(h, w) if hasattr(self.model, "max_batch") else self.batch
+        if limit < 1:
+            raise ValueError("frames of %dx%d are too large: one frame's largest activation would hold 2^31 or more elements, the limit "
+                             "of the convolution kernels (max_batch = 0; 1920x1080 is the largest 16:9 input)" % (w, h))
+        b = min(self.batch, limit)
+        if b < self.batch and (h, w) not in self._told:
+            self._told.add((h, w))
+            print("InferencePipeline: %dx%d frames run in batches of %d instead of %d (the kernels index tensors below 2^31 elements)"
+                  % (w, h, b, self.batch), file=sys.stderr)
+        return b
 
     class _Slot:
         pass
@@ -129,8 +145,8 @@ class InferencePipeline:
         if plan[j] is not None:
             return plan[j]
         sl = self._Slot()
-        sl.host_in = torch.empty((self.batch,) + fmt.shape, dtype=torch.uint8).pin_memory()
-        sl.x = torch.zeros((self.batch,) + fmt.shape, dtype=torch.uint8, device=self.device)
+        sl.host_in = torch.empty((fmt.batch,) + fmt.shape, dtype=torch.uint8).pin_memory()
+        sl.x = torch.zeros((fmt.batch,) + fmt.shape, dtype=torch.uint8, device=self.device)
         sl.fwd = fmt.fwd
         with torch.no_grad():
             side = torch.cuda.Stream(device=self.device)
@@ -175,7 +191,7 @@ class InferencePipeline:
         n = len(frames)
         for i, f in enumerate(frames):
             np.copyto(sl.host_in_np[i], np.asarray(f).reshape(sl.host_in_np.shape[1:]))
-        assert n == self.batch       # (ragged tails run eagerly: InferencePipeline.run)
+        assert n == sl.x.shape[0]    # (ragged tails run eagerly: InferencePipeline.run)
         main = torch.cuda.current_stream()
         sl.x.copy_(sl.host_in, non_blocking=True)
         if sl.graph is not None:
@@ -183,6 +199,8 @@ class InferencePipeline:
         else:
             sl.y = sl.fwd(sl.x)
         sl.done.record(main)
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(device=self.device)
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(sl.done)
             sl.host_out.copy_(sl.y, non_blocking=True)
@@ -197,10 +215,11 @@ class InferencePipeline:
         return out
 
     class _Format:
-        """What a plan is built for: its key in `_plans`, the shape of one input frame, and the device forward of a batch."""
+        """What a plan is built for: its key in `_plans`, the shape of one input frame, the device forward of a batch, and the
+        frames per batch (InferencePipeline._batch_for)."""
 
-        def __init__(self, key, shape, fwd):
-            self.key, self.shape, self.fwd = key, shape, fwd
+        def __init__(self, key, shape, fwd, batch):
+            self.key, self.shape, self.fwd, self.batch = key, shape, fwd, batch
 
     def _out_size(self, h, w, out_size):
         """out_size normalised: None for the network's native size of an h x w input, else (out_h, out_w) as ints."""
@@ -217,38 +236,54 @@ class InferencePipeline:
         return self._run(frames, None, out_size)
 
     def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
-                   out_size=None):
-        """frames: iterable of I420 payloads of h x w (uint8 arrays or bytes of ops.i420_frame_bytes(h, w) each).  Yields the
+                   out_size=None, depth=8, out_depth=None):
+        """frames: iterable of I420 payloads of h x w (uint8 arrays or bytes of ops.i420_frame_bytes(h, w, depth) each).  Yields the
         uint8 I420 payloads of the super-resolved frames (Generator.forward_yuv420 with these colour parameters) in order,
-        batched and pipelined exactly as `run`.  out_size = (out_h, out_w), both even: payloads of that size."""
+        batched and pipelined exactly as `run`.  out_size = (out_h, out_w), both even: payloads of that size.  depth / out_depth
+        (8..16, out_depth defaults to depth): bits per sample in and out; payloads deeper than 8 bits are 2 bytes per sample and
+        still travel as uint8 arrays.  Plans of any pair but (8, 8) append ("depth", depth, out_depth) to the key."""
         colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
                       out_full_range=bool(full_range if out_full_range is None else out_full_range))
         model = self.model
+        depth = check_depth(depth)
+        out_depth = depth if out_depth is None else check_depth(out_depth)
         out_size = self._out_size(h, w, out_size)
         key = ("i420", h, w) + tuple(colour.values()) + (() if out_size is None else ("size",) + out_size)
-        fmt = self._Format(key, (i420_frame_bytes(h, w),), lambda x: model.forward_yuv420(x, h, w, out_size=out_size, **colour))
+        if (depth, out_depth) != (8, 8):
+            key += ("depth", depth, out_depth)
+        fmt = self._Format(key, (i420_frame_bytes(h, w, depth),),
+                           lambda x: model.forward_yuv420(x, h, w, out_size=out_size, depth=depth, out_depth=out_depth, **colour),
+                           self._batch_for(h, w))
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)
 
     def _run(self, frames, fmt, out_size=None):
         it = iter(frames)
         k, inflight = 0, []
+        first = None
+        if fmt is None:                           # RGB frames: plans keyed by (H, W); the first frame says which
+            first = next(it, None)
+            if first is None:
+                return
+            h, w = first.shape[0], first.shape[1]
+            size = self._out_size(h, w, out_size)
+            if size is None:
+                fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8, self._batch_for(h, w))
+            else:
+                fmt = self._Format((h, w, "size") + size, (h, w, 3), lambda x, m=self.model, sz=size: m.forward_u8(x, out_size=sz),
+                                   self._batch_for(h, w))
+        batch = fmt.batch
         while True:
-            chunk = []
-            for f in it:
-                chunk.append(f)
-                if len(chunk) == self.batch:
-                    break
+            chunk = [] if first is None else [first]
+            first = None
+            if len(chunk) < batch:
+                for f in it:
+                    chunk.append(f)
+                    if len(chunk) == batch:
+                        break
             if not chunk:
                 break
-            if fmt is None:                       # RGB frames: plans keyed by (H, W)
-                h, w = chunk[0].shape[0], chunk[0].shape[1]
-                size = self._out_size(h, w, out_size)
-                if size is None:
-                    fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8)
-                else:
-                    fmt = self._Format((h, w, "size") + size, (h, w, 3), lambda x, m=self.model, sz=size: m.forward_u8(x, out_size=sz))
-            if len(chunk) < self.batch:           # the tail (or a bucket smaller than one batch)
+            if len(chunk) < batch:                # the tail (or a bucket smaller than one batch)
                 for sl in inflight:
                     yield from self._collect(sl)
                 inflight = []
@@ -294,7 +329,7 @@ def main(argv=None):
     image_paths = sorted(x for x in os.listdir(args.image_dir)
                          if x.lower().endswith(".png") or x.lower().endswith(".jpg") or x.lower().endswith("jpeg"))
     print(f"Found {len(image_paths)} to super resolve, starting...")
-    pipe = InferencePipeline(model, device, batch=args.batch)
+    pipe = InferencePipeline(model, device, batch=args.batch)      # (reports a batch it has to reduce for large frames, once per size)
     resolve_out_size(1, 1, args.size, args.scale)      # a malformed --size fails before any image is read
 
     def load(name):

@@ -107,8 +107,15 @@ class Generator(torch.nn.Module):
             t = self._forward(ops.u8_to_image(frames), self._cfg_head)
             return ops.resample_image(t.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "u8")
 
+    def max_batch(self, h, w):
+        """Largest batch of h x w frames the convolution kernels can index: every launcher refuses tensors of 2^31 or more elements,
+        and the largest activation of a batch holds n * h * w * n_filters * 4 ** n_upsample of them (the output of the last
+        up-sampling convolution, before its pixel shuffle; with no up-sampling block, the neck's output).  0: a single frame is too large."""
+        nf = self.neck[0].out_channels
+        return (2 ** 31 - 1) // (int(h) * int(w) * nf * 4 ** len(self.upsampling))
+
     def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
-                       out_size=None):
+                       out_size=None, depth=8, out_depth=None):
         """Video inference on planar YUV 4:2:0 frames: (N, bytes) uint8 I420 payloads of h x w (odd sizes legal) in, (N, bytes)
         uint8 I420 payloads of (s h) x (s w) out, s = 2 ** n_upsample.  The input is decoded on the device (matrix "bt601" /
         "bt709", limited or full range, chroma `siting` "jpeg" or "mpeg2") into the generator's [-1, 1] RGB; the head's epilogue
@@ -116,19 +123,28 @@ class Generator(torch.nn.Module):
         which defaults to the input's.  The colour contract is DESIGN.md §6c.
         out_size = (out_h, out_w), both even: payloads of that size instead -- the float head output is resized (antialiased
         bicubic) and encoded by one fused kernel (ops.resample_image).  None or the native size: the head's own
-        epilogue, as before."""
+        epilogue, as before.
+        depth / out_depth (8..16; out_depth defaults to depth): bits per sample of the input / output payloads -- above 8 a
+        sample is 2 bytes, little-endian (ops.i420_frame_bytes(h, w, depth); Y4M's C420p<depth>).  The two are independent
+        (8 -> 10 keeps the precision of the float head that 8-bit codes throw away).  The head's epilogue stays 8-bit: a deeper
+        native-size output is the float head followed by ops.image_to_i420."""
+        depth = ops.check_depth(depth)
+        out_depth = depth if out_depth is None else ops.check_depth(out_depth)
         out_matrix = out_matrix or matrix
         out_full = bool(full_range if out_full_range is None else out_full_range)
         key = (ops.yuv_matrix_code(out_matrix), int(out_full))
-        if not self._native_size(h, w, out_size):
+        native = self._native_size(h, w, out_size)
+        if not native or out_depth != 8:
             with torch.no_grad():
-                t = self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range), self._cfg_head)
-                return ops.resample_image(t.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full)
+                t = self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range, depth), self._cfg_head).permute(0, 2, 3, 1)
+                if native:
+                    return ops.image_to_i420(t, out_matrix, out_full, out_depth)
+                return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth)
         cfg = self._cfg_head_i420.get(key)
         if cfg is None:
             cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
         with torch.no_grad():
-            return self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range), cfg)
+            return self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range, depth), cfg)
 
     def forward(self, x):
         return self._forward(x, self._cfg_head)

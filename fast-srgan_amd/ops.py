@@ -1116,9 +1116,17 @@ def u8_to_image(frames):
     return img.permute(0, 3, 1, 2)
 
 
-def i420_frame_bytes(h, w):
-    """Bytes of one I420 payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) each."""
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+def i420_frame_bytes(h, w, depth=8):
+    """Bytes of one I420 payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) each -- one byte per sample at
+    depth 8, two (little-endian, the value in the low `depth` bits: Y4M's C420p<depth>) at depths 9..16."""
+    return (h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)) * (2 if check_depth(depth) > 8 else 1)
+
+
+def check_depth(depth, lo=8):
+    """The sample depth as an int, refused outside lo..16."""
+    if isinstance(depth, bool) or int(depth) != depth or not lo <= depth <= 16:
+        raise ValueError("sample depth must be an integer in %d..16, got %r" % (lo, depth))
+    return int(depth)
 
 
 YUV_MATRICES = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
@@ -1131,21 +1139,52 @@ def yuv_matrix_code(matrix):
     return YUV_MATRICES[matrix]
 
 
-def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False):
-    """(N, i420_frame_bytes(h, w)) uint8 I420 payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1 of the
+def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False, depth=8):
+    """(N, i420_frame_bytes(h, w, depth)) uint8 I420 payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1 of the
     decoded RGB; chroma upsampled bilinearly at `siting` "jpeg" (centred) or "mpeg2" (co-sited horizontally); DESIGN.md
-    "Video"), the layout u8_to_image returns."""
+    "Video"), the layout u8_to_image returns.  depth 9..16: payloads of 16-bit samples (fsr_i420_to_image_deep), still a uint8 tensor."""
     _check_dev(frames)
+    depth = check_depth(depth)
     if siting not in CHROMA_SITINGS:
         raise ValueError("chroma siting must be one of %s, got %r" % (sorted(CHROMA_SITINGS), siting))
-    if (frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != i420_frame_bytes(h, w) or not frames.is_contiguous()):
-        raise ValueError("i420_to_image expects a contiguous (N, %d) uint8 tensor of %dx%d I420 frames, got %s %s"
-                         % (i420_frame_bytes(h, w), w, h, frames.dtype, tuple(frames.shape)))
+    fb = i420_frame_bytes(h, w, depth)
+    if (frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != fb or not frames.is_contiguous()):
+        raise ValueError("i420_to_image expects a contiguous (N, %d) uint8 tensor of %dx%d %d-bit I420 frames, got %s %s"
+                         % (fb, w, h, depth, frames.dtype, tuple(frames.shape)))
     n = frames.shape[0]
     img = torch.empty((n, h, w, 3), dtype=torch.float32, device=frames.device)
-    L.check(L.lib().fsr_i420_to_image(_p(frames), _p(img), n, h, w, CHROMA_SITINGS[siting], yuv_matrix_code(matrix), int(bool(full_range)),
-                                      _stream()), "fsr_i420_to_image")
+    colour = (CHROMA_SITINGS[siting], yuv_matrix_code(matrix), int(bool(full_range)))
+    if depth == 8:
+        L.check(L.lib().fsr_i420_to_image(_p(frames), _p(img), n, h, w, *colour, _stream()), "fsr_i420_to_image")
+    else:
+        L.check(L.lib().fsr_i420_to_image_deep(_p(frames), _p(img), n, h, w, *colour, depth, _stream()), "fsr_i420_to_image_deep")
     return img.permute(0, 3, 1, 2)
+
+
+def image_to_i420(t_nhwc, matrix="bt601", full_range=False, depth=8):
+    """The I420 encode of DESIGN.md §6c on its own (fsr_image_to_i420): contiguous float32 (N,H,W,3) tanh output, H and W even ->
+    uint8 (N, i420_frame_bytes(H, W, depth)) payloads, depth 8..16 -- what the head's FSR_OUT_I420 epilogue computes, at any depth."""
+    _check_dev(t_nhwc)
+    depth = check_depth(depth)
+    if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
+        raise ValueError("image_to_i420 expects a contiguous float32 (N,H,W,3) tensor, got %s %s" % (t_nhwc.dtype, tuple(t_nhwc.shape)))
+    n, h, w, _ = t_nhwc.shape
+    if h % 2 or w % 2:
+        raise ValueError("I420 output needs even output extents, got %d x %d" % (h, w))
+    out = torch.empty((n, i420_frame_bytes(h, w, depth)), dtype=torch.uint8, device=t_nhwc.device)
+    prof = PROFILE_ENCODE
+    if prof is not None:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+    L.check(L.lib().fsr_image_to_i420(_p(t_nhwc), n, h, w, yuv_matrix_code(matrix), int(bool(full_range)), depth, _p(out), _stream()),
+            "fsr_image_to_i420")
+    if prof is not None:
+        ev1.record()
+        prof.append((ev0, ev1, t_nhwc.numel() * 4 + out.numel()))
+    return out
+
+
+PROFILE_ENCODE = None     # a list: every image_to_i420 launch appends (start event, end event, algorithmic bytes) -- tools/video_bench.py
 
 
 # ---------------------------------------------------------------------------------- arbitrary output size
@@ -1169,14 +1208,18 @@ def aa_taps(in_size, out_size, device):
     return hit
 
 
-def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=False):
+def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=False, depth=8):
     """Antialiased bicubic resize of a head output to out_h x out_w, fused with the output conversion (fsr_resample_image;
     DESIGN.md §6d).  t_nhwc: contiguous float32 (N,H,W,3) tanh output (the NHWC buffer behind Generator.forward's view).
       kind "f32" : float32 (N,3,out_h,out_w) VIEW of an NHWC buffer, 2 v - 1 of the resized c = (t + 1) / 2 -- what
                    F.interpolate(t, mode="bicubic", antialias=True, align_corners=False) returns;
       kind "u8"  : uint8 (N,out_h,out_w,3), (unsigned char)(clamp(v, 0, 1) * 255): forward_u8's bytes at another size;
-      kind "i420": uint8 (N, i420_frame_bytes(out_h, out_w)), the I420 planes of clamp(v, 0, 1) in (matrix, full_range); even extents."""
+      kind "i420": uint8 (N, i420_frame_bytes(out_h, out_w, depth)), the I420 planes of clamp(v, 0, 1) in (matrix, full_range); even
+                   extents; depth 9..16: 16-bit samples (fsr_resample_image_i420_deep).  The other kinds take depth 8 only."""
     _check_dev(t_nhwc)
+    depth = check_depth(depth)
+    if depth != 8 and kind != "i420":
+        raise ValueError("resample_image: depth %d is for kind \"i420\" only" % depth)
     if kind not in RESAMPLE_KINDS:
         raise ValueError("resample_image kind must be one of %s, got %r" % (sorted(RESAMPLE_KINDS), kind))
     if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
@@ -1195,13 +1238,18 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
     elif kind == "u8":
         out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=t_nhwc.device)
     else:
-        out = torch.empty((n, i420_frame_bytes(out_h, out_w)), dtype=torch.uint8, device=t_nhwc.device)
+        out = torch.empty((n, i420_frame_bytes(out_h, out_w, depth)), dtype=torch.uint8, device=t_nhwc.device)
     prof = PROFILE_RESAMPLE
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    L.check(L.lib().fsr_resample_image(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx,
-                                       RESAMPLE_KINDS[kind], mcode, int(bool(full_range)), _p(out), _stream()), "fsr_resample_image")
+    if depth == 8:
+        L.check(L.lib().fsr_resample_image(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx,
+                                           RESAMPLE_KINDS[kind], mcode, int(bool(full_range)), _p(out), _stream()), "fsr_resample_image")
+    else:
+        L.check(L.lib().fsr_resample_image_i420_deep(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin),
+                                                     _p(xsize), kx, mcode, int(bool(full_range)), depth, _p(out), _stream()),
+                "fsr_resample_image_i420_deep")
     if prof is not None:
         ev1.record()
         prof.append((ev0, ev1, t_nhwc.numel() * 4 + out.numel() * out.element_size()))

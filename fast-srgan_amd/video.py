@@ -11,6 +11,11 @@ RGB (fsr_i420_to_image) and the head's epilogue stores finished I420 planes (FSR
 1080p is `--size 1920x1080` or `--scale 3`; the default is the network's 4x.  The resize is the antialiased bicubic fused with the
 I420 encode after the head, inside the same graph replay.
 
+Streams of 9- to 16-bit samples (`C420p10` and its kin: what `ffmpeg -f yuv4mpegpipe` emits for HEVC Main10, AV1 or VP9 profile 2
+sources) are read as they are -- 2 bytes per sample, little-endian -- and `--out_depth` picks the depth of the output, the
+input's by default: `--out_depth 10` on an 8-bit source keeps the precision of the float head that 256 levels throw away.
+`C420pN` cannot declare a chroma siting; `--siting mpeg2` says what the stream cannot (HD sources are normally left-sited).
+
 Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
 stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
 device batch at a time: a stream of any length passes through a pipe.
@@ -21,7 +26,7 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from .ops import i420_frame_bytes
+from .ops import check_depth, i420_frame_bytes
 
 MATRICES = ("bt601", "bt709")
 SITINGS = ("jpeg", "mpeg2")
@@ -38,10 +43,15 @@ _REJECTED_C = ("420paldv", "411", "422", "444", "444alpha", "mono")
 
 class Y4MReader:
     """Streaming reader: parses the stream header on construction, then `frames()` yields one uint8 payload
-    (i420_frame_bytes(height, width) bytes, a numpy array) per FRAME, reading only that frame from the file."""
+    (i420_frame_bytes(height, width, depth) bytes, a numpy array) per FRAME, reading only that frame from the file.
+    max_depth: the deepest samples the caller takes.  The default, 8, refuses `C420pN` streams: their payloads are 16-bit
+    little-endian samples, which a caller that indexes bytes must not be handed silently.  With max_depth >= 9, `C420pN` for
+    9 <= N <= max_depth is accepted (`.depth` = N, `.frame_bytes` twice the sample count; siting "jpeg": the tag declares none)."""
 
-    def __init__(self, f):
+    def __init__(self, f, max_depth=8):
         self.f = f
+        self.max_depth = check_depth(max_depth)
+        self.depth = 8
         line = f.readline()
         if not line.startswith(b"YUV4MPEG2"):
             raise Y4MError("Y4M: the stream does not start with the YUV4MPEG2 signature")
@@ -77,17 +87,28 @@ class Y4MReader:
                     self.colour_range = r.lower()
         if not self.width or not self.height or self.width <= 0 or self.height <= 0:
             raise Y4MError("Y4M: the stream header lacks the frame size (tags 'W' and 'H')")
-        self.frame_bytes = i420_frame_bytes(self.height, self.width)
+        self.frame_bytes = i420_frame_bytes(self.height, self.width, self.depth)
 
-    @staticmethod
-    def _colour_space(val):
+    def _colour_space(self, val):
+        takes = "4:2:0 8-bit only: C420jpeg, C420mpeg2" if self.max_depth == 8 else \
+            "4:2:0 only: C420jpeg, C420mpeg2, C420p9..C420p%d" % self.max_depth
         if val in _ACCEPTED_C:
+            self.depth = 8
             return _ACCEPTED_C[val]
         if val in _REJECTED_C:
-            raise Y4MError("Y4M: colour space 'C%s' is not supported (4:2:0 8-bit only: C420jpeg, C420mpeg2)" % val)
+            raise Y4MError("Y4M: colour space 'C%s' is not supported (%s)" % (val, takes))
         if "p" in val and val.split("p")[-1].isdigit():
-            raise Y4MError("Y4M: colour space 'C%s' is deeper than 8 bits (4:2:0 8-bit only)" % val)
-        raise Y4MError("Y4M: unknown colour space 'C%s' (4:2:0 8-bit only: C420jpeg, C420mpeg2)" % val)
+            base, bits = val.rsplit("p", 1)
+            if self.max_depth == 8:
+                raise Y4MError("Y4M: colour space 'C%s' is deeper than 8 bits (4:2:0 8-bit only)" % val)
+            if base != "420":
+                raise Y4MError("Y4M: colour space 'C%s' is not supported (%s)" % (val, takes))
+            if not 9 <= int(bits) <= self.max_depth:
+                raise Y4MError("Y4M: colour space 'C%s': %s bits per sample are outside what this reader takes (9..%d)"
+                               % (val, bits, self.max_depth))
+            self.depth = int(bits)
+            return "jpeg"
+        raise Y4MError("Y4M: unknown colour space 'C%s' (%s)" % (val, takes))
 
     def frames(self):
         idx = 0
@@ -109,11 +130,13 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes the stream header on construction (C420jpeg, XCOLORRANGE of the output range), then one FRAME per payload."""
+    """Writes the stream header on construction (C420jpeg, or C420p<depth> for samples deeper than 8 bits; XCOLORRANGE of the
+    output range), then one FRAME per payload."""
 
-    def __init__(self, f, width, height, frame_rate=None, aspect=None, interlace=None, full_range=False):
+    def __init__(self, f, width, height, frame_rate=None, aspect=None, interlace=None, full_range=False, depth=8):
         self.f = f
-        self.frame_bytes = i420_frame_bytes(height, width)
+        self.depth = check_depth(depth)
+        self.frame_bytes = i420_frame_bytes(height, width, self.depth)
         tags = ["W%d" % width, "H%d" % height]
         if frame_rate is not None:
             tags.append("F" + frame_rate)
@@ -121,7 +144,7 @@ class Y4MWriter:
             tags.append("I" + interlace)
         if aspect is not None:
             tags.append("A" + aspect)
-        tags += ["C420jpeg", "XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")]
+        tags += ["C420jpeg" if self.depth == 8 else "C420p%d" % self.depth, "XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")]
         f.write(("YUV4MPEG2 " + " ".join(tags) + "\n").encode("ascii"))
 
     def write_frame(self, payload):
@@ -141,6 +164,9 @@ parser.add_argument("--matrix", default="bt601", choices=MATRICES, help="colour 
 parser.add_argument("--range", default="limited", choices=["limited", "full"], help="input range (XCOLORRANGE overrides it)")
 parser.add_argument("--out_matrix", default=None, choices=MATRICES, help="colour matrix of the output (default: the input's)")
 parser.add_argument("--out_range", default=None, choices=["limited", "full"], help="output range (default: the input's)")
+parser.add_argument("--out_depth", default=None, type=int, choices=[8, 10, 12, 16], help="bits per sample of the output (default: the input's)")
+parser.add_argument("--siting", default=None, choices=SITINGS,
+                    help="chroma siting of the input, overriding the stream's tag (C420pN streams cannot declare one: jpeg is assumed)")
 _size_flags = parser.add_mutually_exclusive_group()
 _size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="exact output size, both even (default: 4x the input)")
 _size_flags.add_argument("--scale", default=None, type=float, help="output size relative to the INPUT, rounded to even numbers")
@@ -165,7 +191,9 @@ def main(argv=None):
     fin = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
     fout = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
     try:
-        reader = Y4MReader(fin)
+        reader = Y4MReader(fin, max_depth=16)
+        siting = args.siting or reader.siting
+        out_depth = reader.depth if args.out_depth is None else args.out_depth
         full = (reader.colour_range or args.range) == "full"
         out_full = full if args.out_range is None else args.out_range == "full"
         out_matrix = args.out_matrix or args.matrix
@@ -175,21 +203,26 @@ def main(argv=None):
         h, w = reader.height, reader.width
         out_size = resolve_out_size(h, w, args.size, args.scale, even=True)
         oh, ow = out_size or (s * h, s * w)
-        _status("video: %dx%d -> %dx%d%s, %s %s -> %s %s, chroma siting %s" % (
+        _status("video: %dx%d -> %dx%d%s, %s %s %d-bit -> %s %s %d-bit, chroma siting %s" % (
             w, h, ow, oh, "" if out_size is None else " (network %dx%d, resized)" % (s * w, s * h),
-            args.matrix, "full" if full else "limited", out_matrix, "full" if out_full else "limited", reader.siting))
-        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full)
+            args.matrix, "full" if full else "limited", reader.depth, out_matrix, "full" if out_full else "limited", out_depth, siting))
         pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False)
+        try:
+            frames_out = pipe.run_yuv420(reader.frames(), h, w, siting=siting, matrix=args.matrix, full_range=full, out_matrix=out_matrix,
+                                         out_full_range=out_full, out_size=out_size, depth=reader.depth, out_depth=out_depth)
+        except ValueError as exc:       # a frame too large for the kernels: refused before anything is allocated or written
+            raise SystemExit("video: %s" % exc)
+        batch = min(args.batch, model.max_batch(h, w))      # (the pipeline has reported a batch it had to reduce)
+        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth)
         n, t0, t1 = 0, time.perf_counter(), None
-        for y in pipe.run_yuv420(reader.frames(), h, w, siting=reader.siting, matrix=args.matrix, full_range=full,
-                                 out_matrix=out_matrix, out_full_range=out_full, out_size=out_size):
+        for y in frames_out:
             writer.write_frame(y)       # (a view of the pinned result buffer: written before the slot is reused)
             n += 1
-            if n == args.batch:
+            if n == batch:
                 t1 = time.perf_counter()   # the first batch carries the plan's warm-up and graph capture
         fout.flush()
         t2 = time.perf_counter()
-        steady = "%.1f fps after the first batch" % ((n - args.batch) / (t2 - t1)) if t1 is not None and n > args.batch else "-"
+        steady = "%.1f fps after the first batch" % ((n - batch) / (t2 - t1)) if t1 is not None and n > batch else "-"
         _status("video: %d frames in %.3f s (%s)" % (n, t2 - t0, steady))
     finally:
         if fin is not sys.stdin.buffer:

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 12
+#define FSR_ABI_VERSION 13
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
@@ -244,6 +244,20 @@ int fsr_u8_to_image(const uint8_t* frames, float* img, long long count, fsr_stre
 int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,
                       fsr_stream_t stream);
 
+/* Deep samples (ABI 13): an I420 payload of depth 9 <= d <= 16 has the plane order and extents above with every
+ * sample in 2 bytes, little-endian, the value in the low d bits (what Y4M C420p<d> carries) -- twice the bytes of an 8-bit payload.
+ *   limited range: Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8);  full range: Y = (2^d - 1) E_Y, C = 2^(d-1) + (2^d - 1) E_C;
+ *   encode: code = clamp(floor(v + 0.5), 0, 2^d - 1);  d = 8 gives the 8-bit numbers.
+ * fsr_i420_to_image_deep: fsr_i420_to_image for such payloads (frames 2-byte aligned; depth outside 9..16 is refused; a stored value
+ * above 2^d - 1 is taken as it is -- the clamp of R, G, B to [0, 1] deals with it). */
+int fsr_i420_to_image_deep(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range, int depth,
+                           fsr_stream_t stream);
+
+/* The encode on its own: float tanh output t [n,h,w,3] (h, w even) -> n I420 payloads at `depth` 8..16 (uint8 samples for 8, 16-bit
+ * samples above) -- c = clamp((t + 1) / 2, 0, 1), Y per pixel, Cb / Cr the mean of E_C over each 2x2 block (C420jpeg siting), the
+ * arithmetic and summation order of fsr_conv3x3's FSR_OUT_I420 epilogue.  One streaming kernel; n * h * w stays below 2^31. */
+int fsr_image_to_i420(const float* t, int n, int h, int w, int matrix, int full_range, int depth, void* out, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ arbitrary output size: antialiased bicubic resize of the head output
  * t: the head's float tanh output [n,h,w,3] (FSR_OUT_F32 of any dtype's head) -> an oh x ow image in ONE fused kernel (horizontal pass
  * of a tile's source-row window into LDS, vertical pass from LDS, conversion, store; no global intermediate, no atomics).  The
@@ -260,6 +274,11 @@ int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, in
 int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
                        const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int yuv_matrix, int yuv_full_range,
                        void* out, fsr_stream_t stream);
+/* ... with FSR_OUT_I420 planes of 16-bit samples at depth 9..16 (ABI 13; the deep payload of fsr_i420_to_image_deep): the same kernel
+ * with a 16-bit code type in its I420 stage. */
+int fsr_resample_image_i420_deep(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize,
+                                 int ky, const float* wx, const int* xmin, const int* xsize, int kx, int yuv_matrix, int yuv_full_range,
+                                 int depth, void* out, fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ first-layer convolutions straight from the image
  * Conv2d(3 -> cout, k3, p1) of Generator.neck (model.py:75-78), Discriminator.neck (model.py:143-146) and

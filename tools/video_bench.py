@@ -14,8 +14,15 @@
      then (a) and (b) again for forward_yuv420, and the resample kernel alone from its own events (ops.PROFILE_RESAMPLE) with its
      achieved bytes/s over its algorithmic bytes: 12 B per source pixel + 3 (RGB) or 1.5 (I420) B per output pixel.
 
+  4. `--deep`: samples deeper than 8 bits.  360x640, batch 8, f16, every path one hipGraph, device events,
+     interleaved round by round:
+       (a) forward_yuv420, 8 bits in and out (the head's I420 epilogue);   (b) 10 bits in, 10 bits out;   (c) 8 bits in, 10 bits out
+     -- (b) and (c) are the float head followed by the encode kernel -- then the encode kernel alone from its own events
+     (ops.PROFILE_ENCODE) over its algorithmic bytes: 12 B in + 3 B out per pixel.
+
     python tools/video_bench.py [--frames 2048] [--rounds 7] [--replays 20] [--modes f16,x3]
     python tools/video_bench.py --resize [--rounds 7] [--replays 20]
+    python tools/video_bench.py --deep [--rounds 7] [--replays 20]
 """
 import argparse
 import importlib
@@ -154,6 +161,51 @@ def resize_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, size=(1080, 1
     return med
 
 
+def deep_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
+    dev = "cuda:0"
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+    x8 = torch.from_numpy(rng.integers(0, 256, size=(b, ops.i420_frame_bytes(h, w)), dtype=np.uint8)).to(dev)
+    deep = rng.integers(0, 2 ** d, size=(b, ops.i420_frame_bytes(h, w)), dtype=np.uint16)
+    xd = torch.from_numpy(np.ascontiguousarray(deep.astype("<u2")).view(np.uint8)).to(dev)
+    paths = [("8 in, 8 out (head epilogue)", graphed(lambda x: G.forward_yuv420(x, h, w), x8)),
+             ("%d in, %d out" % (d, d), graphed(lambda x: G.forward_yuv420(x, h, w, depth=d), xd)),
+             ("8 in, %d out" % d, graphed(lambda x: G.forward_yuv420(x, h, w, out_depth=d), x8))]
+    times = [[] for _ in paths]
+    for _, g in paths:
+        time_graph(g, 3)
+    for r in range(rounds):
+        order = list(range(len(paths)))
+        for i in (order if r % 2 == 0 else order[::-1]):
+            times[i].append(time_graph(paths[i][1], replays))
+    med = [statistics.median(t) for t in times]
+    for (name, _), m, t in zip(paths, med, times):
+        print("deep        %-4s batch %d %dx%d  yuv420 %-28s %7.3f ms/batch  %7.1f FPS   [per-round ms %s]" % (
+            mode, b, h, w, name, 1e3 * m, b / m, " ".join("%.3f" % (1e3 * v) for v in t)), flush=True)
+    print("deep        %d/%d - 8/8: %+.3f ms per batch (%+.2f %%);  8/%d - 8/8: %+.3f ms per batch (%+.2f %%)" % (
+        d, d, 1e3 * (med[1] - med[0]), 100.0 * (med[1] / med[0] - 1.0), d, 1e3 * (med[2] - med[0]), 100.0 * (med[2] / med[0] - 1.0)), flush=True)
+    # the encode kernel alone, from its own events, on a real head output
+    with torch.no_grad():
+        t = G(ops.i420_to_image(x8, h, w)).permute(0, 2, 3, 1)
+    for depth in (8, d):
+        for _ in range(5):
+            ops.image_to_i420(t, depth=depth)
+        torch.cuda.synchronize()
+        ops.PROFILE_ENCODE = []
+        for _ in range(50):
+            ops.image_to_i420(t, depth=depth)
+        torch.cuda.synchronize()
+        prof, ops.PROFILE_ENCODE = ops.PROFILE_ENCODE, None
+        ms = sorted(e0.elapsed_time(e1) for e0, e1, _ in prof)
+        nbytes = prof[0][2]
+        print("deep        kernel image_to_i420_kernel<%s> %dx%d batch %d: median %.1f us, min %.1f us (own events, 50 launches); "
+              "%.1f MB algorithmic -> %.2f TB/s at the median" % ("u8" if depth == 8 else "u16", 4 * h, 4 * w, b, 1e3 * ms[len(ms) // 2],
+                                                               1e3 * ms[0], nbytes / 1e6, nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
+    return med
+
+
 def end_to_end(sd, frames, mode):
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "configs"))
@@ -191,6 +243,7 @@ def main():
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--modes", default="f16,x3")
     ap.add_argument("--resize", action="store_true", help="run the arbitrary-output-size leg only")
+    ap.add_argument("--deep", action="store_true", help="run the deep-sample leg only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("video_bench needs the MI355X")
@@ -198,6 +251,9 @@ def main():
     print("device:", torch.cuda.get_device_name(0), flush=True)
     if args.resize:
         resize_leg(sd, args.rounds, args.replays)
+        return
+    if args.deep:
+        deep_leg(sd, args.rounds, args.replays)
         return
     model = {}
     for mode in args.modes.split(","):
