@@ -53,6 +53,70 @@ template <> __device__ __forceinline__ float round_T<float>(float v) { return v;
 template <> __device__ __forceinline__ float round_T<bf16_t>(float v) { return bf2f(f2bf(v)); }
 template <> __device__ __forceinline__ float round_T<f16_t>(float v) { return (float)(f16_t)v; }
 
+// Ablation builds (tools/build_variant.sh <suffix> -DFSR_ABLC3=<mask>; results WRONG on purpose, the product library is built
+// with 0):  1 no output stores (forward) / no dz loads (weight gradient)   2 no MFMAs   4 no LDS traffic of the dz tile
+// (weight gradient; implies 2): 6 leaves the weight gradient's global loads alone
+#ifndef FSR_ABLC3
+#define FSR_ABLC3 0
+#endif
+constexpr int C3_ABL = FSR_ABLC3;
+// keeps a value (and the instructions that made it) alive in a build that drops its store
+#if FSR_ABLC3
+#define C3_KEEP(v) asm volatile("" ::"v"(v))
+#else
+#define C3_KEEP(v) ((void)0)
+#endif
+
+// The patch of stage_patch below in two halves, for the weight gradient's pipelined tile loop, which keeps the loads in
+// flight over its MFMAs: `load` issues every global load of the thread (out-of-image addresses clamped to the image origin,
+// values discarded, as below), `commit` normalises and writes LDS.  The forward keeps stage_patch: routed through these
+// helpers its x3 form measured 19 % slower (profiles/c3_stream_ablation.txt).
+template <int TH> struct PatchRegs {
+  static constexpr int PN = (TH + 2) * PW * 3;
+  static constexpr int PPT = (PN + 255) / 256;
+  float v[PPT];
+  unsigned okmask;
+};
+template <int TH>
+__device__ __forceinline__ void patch_load(const C3Args& a, PatchRegs<TH>& r, int n, int y0, int x0, int tid) {
+  const float* src = a.img + n * a.sn;
+  r.okmask = 0u;
+#pragma unroll
+  for (int j = 0; j < PatchRegs<TH>::PPT; ++j) {
+    const int i = tid + j * 256;
+    const int ci = i % 3, p = i / 3;
+    const int px = p % PW, py = p / PW;
+    const int y = y0 - 1 + py, x = x0 - 1 + px;
+    const bool ok = i < PatchRegs<TH>::PN && y >= 0 && y < a.H && x >= 0 && x < a.W;
+    r.okmask |= (ok ? 1u : 0u) << j;
+    r.v[j] = src[ok ? ci * a.sc + y * a.sh + x * a.sw : 0];
+  }
+}
+// this thread's scale / shift per patch element (element i = tid + 256 j is channel i % 3 for every tile): registers, set
+// once per kernel.  FSR_TOUCH keeps them there: left to itself the compiler turns the select chain of a pipelined
+// caller into an indexed load of the kernel arguments, one memory round trip per element between two barriers.
+template <int TH> struct PatchNorm {
+  float sc[PatchRegs<TH>::PPT], sh[PatchRegs<TH>::PPT];
+};
+template <int TH>
+__device__ __forceinline__ void patch_norm(const C3Args& a, PatchNorm<TH>& q, int tid) {
+#pragma unroll
+  for (int j = 0; j < PatchRegs<TH>::PPT; ++j) {
+    const int ci = (tid + j * 256) % 3;
+    q.sc[j] = ci == 0 ? a.scale[0] : (ci == 1 ? a.scale[1] : a.scale[2]);
+    q.sh[j] = ci == 0 ? a.shift[0] : (ci == 1 ? a.shift[1] : a.shift[2]);
+    FSR_TOUCH(q.sc[j]);
+    FSR_TOUCH(q.sh[j]);
+  }
+}
+template <typename T, int TH>
+__device__ __forceinline__ void patch_commit(const PatchNorm<TH>& q, const PatchRegs<TH>& r, float* patch, int tid) {
+#pragma unroll
+  for (int j = 0; j < PatchRegs<TH>::PPT; ++j) {
+    const int i = tid + j * 256;
+    if (i < PatchRegs<TH>::PN) patch[i] = ((r.okmask >> j) & 1u) ? round_T<T>(r.v[j] * q.sc[j] + q.sh[j]) : 0.f;
+  }
+}
 // stage rows [y0-1, y0+TH] x cols [x0-1, x0+16] of image n, normalised and rounded to T, as floats.
 // All loads of a thread are issued before the first use: the address of an out-of-image element is clamped to the
 // image origin and its value discarded (a load under a divergent branch is followed by its own s_waitcnt, which made
@@ -177,7 +241,10 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
       if (wide) {
         f32x4 acc[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = mfma16<T>(wf16[t], xf16, (f32x4){0.f, 0.f, 0.f, 0.f});
+        for (int t = 0; t < 4; ++t) {
+          if constexpr ((C3_ABL & 2) != 0) acc[t] = (f32x4){xv[t], xv[t + 4], xv[t], xv[t + 4]};
+          else acc[t] = mfma16<T>(wf16[t], xf16, (f32x4){0.f, 0.f, 0.f, 0.f});
+        }
         if (gx < a.W && gy < a.H) {
           const size_t off = (((size_t)n * a.H + gy) * a.W + gx) * a.cout + nb * 64 + lg * 8;
 #pragma unroll
@@ -194,7 +261,8 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
               hi[q] = fmaxf(hi[q], 0.f) + slope * fminf(hi[q], 0.f);
             }
             const u32x4 pk = (u32x4){pack2<T>(lo[0], lo[1]), pack2<T>(lo[2], lo[3]), pack2<T>(hi[0], hi[1]), pack2<T>(hi[2], hi[3])};
-            fsr_st<4>((u32x4*)((T*)outp + off + p * 32), pk);
+            if constexpr ((C3_ABL & 1) != 0) C3_KEEP(pk);
+            else fsr_st<4>((u32x4*)((T*)outp + off + p * 32), pk);
             if (a.signs) {      // the lane's eight channels nb * 64 + p * 32 + lg * 8 .. + 7 as one byte of sign bits of the STORED values
               unsigned b = 0u;
 #pragma unroll
@@ -213,7 +281,10 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
         for (int t = 0; t < 4; ++t) {
           acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int j = 0; j < 8; ++j) acc[t] = mfma_f32_16x16x4(wf32[t][j], xv[j], acc[t]);
+          for (int j = 0; j < 8; ++j) {
+            if constexpr ((C3_ABL & 2) != 0) acc[t][j & 3] += wf32[t][j] + xv[j];
+            else acc[t] = mfma_f32_16x16x4(wf32[t][j], xv[j], acc[t]);
+          }
         }
         if (gx < a.W && gy < a.H) {
           const size_t off = (((size_t)n * a.H + gy) * a.W + gx) * a.cout + nb * 64 + lg * 8;
@@ -224,7 +295,12 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
             if (prep) V16<x3_t, 4>::st((x3_t*)prep + off + p * 32, v8);
 #pragma unroll
             for (int q = 0; q < 8; ++q) v8[q] = fmaxf(v8[q], 0.f) + slope * fminf(v8[q], 0.f);
-            V16<x3_t, 4>::st((x3_t*)outp + off + p * 32, v8);
+            if constexpr ((C3_ABL & 1) != 0) {
+#pragma unroll
+              for (int q = 0; q < 8; ++q) C3_KEEP(v8[q]);
+            } else {
+              V16<x3_t, 4>::st((x3_t*)outp + off + p * 32, v8);
+            }
           }
         }
         continue;
@@ -277,11 +353,23 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
 // ------------------------------------------------------------------ weight gradient
 // Workgroup = a slab of 8x16-pixel tiles; wave w owns output channels [16w, 16w+16) of the current 64-channel block
 // (blockIdx.y) x 32 patch columns: two accumulators for the whole slab.
+//
+// The tile loop is software-pipelined: the global loads of tile i+1 (dz units and patch values) are issued into registers
+// BEFORE the MFMAs of tile i and written to LDS after them, so the matrix pipe (64 f32 MFMAs per wave and tile in the
+// f32 / x3 forms: about half of the tile's HBM time) runs under the loads instead of after them.  ONE LDS image, two barriers
+// per tile: two images (one barrier) halve the workgroups per CU and measured no faster than the serial loop
+// (profiles/c3_stream_ablation.txt).
+// f32 / x3 dz tile: [128 px][64 co] floats with NO pitch pad; pixel p keeps channel c at column (c + 16 (p & 3)) & 63.
+// The MFMA loop's ds_read_b32 has lane group lg on pixel 4 (s & 3) + lg, i.e. p & 3 = lg, and lanes l15 on consecutive
+// channels: bank (16 wave + l15 + 16 lg) & 63, all 64 lanes on different banks (what the 16-float pad bought before, in
+// 32,768 instead of 40,960 bytes: four workgroups per CU instead of three, = the 1024 slabs in one round).
 template <typename T, typename ST = T>
 __global__ __launch_bounds__(256) void conv_c3_wgrad_kernel(const C3Args a) {
   constexpr int TH = 8;
-  constexpr int PA = 64 + 16;                     // dz tile pitch (elements): [128 px][64 co]
-  __shared__ float patch[(TH + 2) * PW * 3];
+  constexpr bool F32 = sizeof(T) == 4;
+  constexpr int PA = F32 ? 64 : 64 + 16;          // dz tile pitch (elements): [128 px][64 co]
+  constexpr int PN = (TH + 2) * PW * 3;
+  __shared__ float patch[PN];
   __shared__ __attribute__((aligned(16))) T dzt[TH * 16 * PA];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lg = lane >> 4;
@@ -291,6 +379,10 @@ __global__ __launch_bounds__(256) void conv_c3_wgrad_kernel(const C3Args a) {
   const ST* dzg = (const ST*)a.dz;
   constexpr int EPB = 16 / (int)sizeof(T);
   constexpr bool X3 = std::is_same<ST, x3_t>::value;
+  // 16-byte units of the dz tile per thread: x3 = 8-channel units (16 bytes of hi + 16 of lo), else EPB-channel units
+  constexpr int UPP = X3 ? 8 : 64 / EPB;          // units per pixel
+  constexpr int DPT = TH * 16 * UPP / 256;
+  static_assert((TH * 16 * UPP) % 256 == 0, "dz tile units per thread");
 
   // patch offsets of this lane's two columns j = l15 and j = 16 + l15 (k = column index; k >= 27 is padding)
   const int off0 = patch_off(l15), off1 = (16 + l15 < 27) ? patch_off(16 + l15) : -1;
@@ -301,90 +393,116 @@ __global__ __launch_bounds__(256) void conv_c3_wgrad_kernel(const C3Args a) {
 
   const int t0 = slab * a.tiles_per_slab;
   const int t1 = (t0 + a.tiles_per_slab < a.ntiles) ? t0 + a.tiles_per_slab : a.ntiles;
-  for (int tile = t0; tile < t1; ++tile) {
+
+  // the registers a tile travels in between its global loads and its LDS image
+  PatchRegs<TH> pr;
+  PatchNorm<TH> pq;
+  patch_norm<TH>(a, pq, tid);
+  u32x4 dv[DPT], dl[X3 ? DPT : 1];
+  // every global load of a tile, all issued before the first use (a load consumed under its own branch costs one memory
+  // round trip each); out-of-image / out-of-block units read the tensor's first bytes and are zeroed
+  auto load_tile = [&](int tile) {
     const int tx = tile % a.tiles_x;
     const int ty = (tile / a.tiles_x) % a.tiles_y;
     const int n = tile / (a.tiles_x * a.tiles_y);
-    __syncthreads();
-    stage_patch<T, TH>(a, patch, n, ty * TH, tx * 16, tid);
-    if constexpr (X3) {   // x3 dz -> float tile: 8-channel units, hi and lo 16 bytes each, joined on the way to LDS
-      constexpr int DU = TH * 16 * 8, DPT = DU / 256;
-      u32x4 dh[DPT], dl[DPT];
+    patch_load<TH>(a, pr, n, ty * TH, tx * 16, tid);
 #pragma unroll
-      for (int j = 0; j < DPT; ++j) {
-        const int u = tid + j * 256;
-        const int unit = u % 8, p = u / 8;
-        const int y = ty * TH + p / 16, x = tx * 16 + (p & 15);
+    for (int j = 0; j < DPT; ++j) {
+      const int u = tid + j * 256;
+      const int unit = u % UPP, p = u / UPP;
+      const int y = ty * TH + p / 16, x = tx * 16 + (p & 15);
+      if constexpr ((C3_ABL & 1) != 0) {
+        dv[j] = (u32x4){(unsigned)u, 0u, 0u, 0u};
+        if constexpr (X3) dl[j] = (u32x4){0u, 0u, 0u, 0u};
+      } else if constexpr (X3) {
         const bool ok = y < a.H && x < a.W && unit * 8 < cvalid;
         const char* hp = (const char*)x3_hi_ptr(dzg + (ok ? (((size_t)n * a.H + y) * a.W + x) * a.cout + nb * 64 + unit * 8 : 0));
-        const u32x4 th = *(const u32x4*)hp, tl = *(const u32x4*)(hp + 64);
-        dh[j] = ok ? th : (u32x4){0u, 0u, 0u, 0u};
+        // (x3_hi_ptr's integer arithmetic loses the address space: as flat loads these would also count on lgkmcnt,
+        // and the MFMA loop's first LDS wait would wait for them)
+        const u32x4 th = *FSR_GLOBAL_PTR(const u32x4, hp), tl = *FSR_GLOBAL_PTR(const u32x4, hp + 64);
+        dv[j] = ok ? th : (u32x4){0u, 0u, 0u, 0u};
         dl[j] = ok ? tl : (u32x4){0u, 0u, 0u, 0u};
-      }
-#pragma unroll
-      for (int j = 0; j < DPT; ++j) {
-        const int u = tid + j * 256;
-        float* d = (float*)dzt + (u / 8) * PA + (u % 8) * 8;
-        *(f32x4*)d = (f32x4){x3_join_lo(dh[j][0], dl[j][0]), x3_join_hi(dh[j][0], dl[j][0]), x3_join_lo(dh[j][1], dl[j][1]), x3_join_hi(dh[j][1], dl[j][1])};
-        *(f32x4*)(d + 4) = (f32x4){x3_join_lo(dh[j][2], dl[j][2]), x3_join_hi(dh[j][2], dl[j][2]), x3_join_lo(dh[j][3], dl[j][3]), x3_join_hi(dh[j][3], dl[j][3])};
-      }
-    } else {   // dz tile: all loads of a thread first, then the LDS writes (a load consumed under its own branch costs one
-        // memory round trip each)
-      constexpr int DU = TH * 16 * (64 / EPB), DPT = DU / 256;
-      static_assert(DU % 256 == 0, "dz tile units per thread");
-      u32x4 dv[DPT];
-#pragma unroll
-      for (int j = 0; j < DPT; ++j) {
-        const int u = tid + j * 256;
-        const int unit = u % (64 / EPB), p = u / (64 / EPB);
-        const int y = ty * TH + p / 16, x = tx * 16 + (p & 15);
+      } else {
         const bool ok = y < a.H && x < a.W && unit * EPB < cvalid;
         const u32x4 t = *(const u32x4*)((const T*)dzg + (ok ? (((size_t)n * a.H + y) * a.W + x) * a.cout + nb * 64 + unit * EPB : 0));
         dv[j] = ok ? t : (u32x4){0u, 0u, 0u, 0u};
       }
+    }
+  };
+  auto commit_tile = [&]() {
+    patch_commit<T, TH>(pq, pr, patch, tid);
 #pragma unroll
-      for (int j = 0; j < DPT; ++j) {
-        const int u = tid + j * 256;
-        *(u32x4*)(dzt + (u / (64 / EPB)) * PA + (u % (64 / EPB)) * EPB) = dv[j];
+    for (int j = 0; j < DPT; ++j) {
+      const int u = tid + j * 256;
+      const int unit = u % UPP, p = u / UPP;
+      if constexpr ((C3_ABL & 4) != 0) {
+        C3_KEEP(dv[j]);
+        if constexpr (X3) C3_KEEP(dl[j]);
+      } else if constexpr (X3) {   // x3 dz -> float tile: hi and lo joined on the way to LDS
+        float* d = (float*)dzt + p * PA + ((unit * 8 + 16 * (p & 3)) & 63);
+        *(f32x4*)d = (f32x4){x3_join_lo(dv[j][0], dl[j][0]), x3_join_hi(dv[j][0], dl[j][0]), x3_join_lo(dv[j][1], dl[j][1]), x3_join_hi(dv[j][1], dl[j][1])};
+        *(f32x4*)(d + 4) = (f32x4){x3_join_lo(dv[j][2], dl[j][2]), x3_join_hi(dv[j][2], dl[j][2]), x3_join_lo(dv[j][3], dl[j][3]), x3_join_hi(dv[j][3], dl[j][3])};
+      } else if constexpr (F32) {
+        *(u32x4*)(dzt + p * PA + ((unit * EPB + 16 * (p & 3)) & 63)) = dv[j];
+      } else {
+        *(u32x4*)(dzt + p * PA + unit * EPB) = dv[j];
       }
+    }
+  };
+
+  if (t0 < t1) {
+    load_tile(t0);
+    commit_tile();
+  }
+  __syncthreads();
+  for (int tile = t0; tile < t1; ++tile) {
+    const bool more = tile + 1 < t1;              // (uniform)
+    if (more) load_tile(tile + 1);
+    if (active && (C3_ABL & 6) == 0) {
+      const T* dzc = dzt;
+      const float* pc = patch;
+      if constexpr (sizeof(T) == 2) {
+        // K step = 32 pixels = tile rows 2s, 2s+1; lane group lg owns pixels 8lg..8lg+7: row 2s + (lg>>1), cols 8(lg&1)+e
+        const int qrow = l15 >> 2, qch = (l15 & 3) * 4;
+#pragma unroll
+        for (int s = 0; s < TH / 2; ++s) {
+          const int r = 2 * s + (lg >> 1), c0 = 8 * (lg & 1);
+          const T* pa = dzc + (r * 16 + c0 + qrow) * PA + wave * 16 + qch;
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(FSR_LDS_PTR(s16x4, pa));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(FSR_LDS_PTR(s16x4, pa + 4 * PA));
+          const s16x8 af = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          const float* pb = pc + (r * PW + c0) * 3;
+          float b0[8], b1[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            b0[e] = pb[e * 3 + off0];
+            b1[e] = off1 >= 0 ? pb[e * 3 + off1] : ones27;
+          }
+          const s16x8 bf0 = __builtin_bit_cast(s16x8, (u32x4){pack2<T>(b0[0], b0[1]), pack2<T>(b0[2], b0[3]),
+                                                             pack2<T>(b0[4], b0[5]), pack2<T>(b0[6], b0[7])});
+          const s16x8 bf1 = __builtin_bit_cast(s16x8, (u32x4){pack2<T>(b1[0], b1[1]), pack2<T>(b1[2], b1[3]),
+                                                             pack2<T>(b1[4], b1[5]), pack2<T>(b1[6], b1[7])});
+          acc0 = mfma16<T>(af, bf0, acc0);
+          acc1 = mfma16<T>(af, bf1, acc1);
+        }
+      } else {
+        // K step = 4 pixels of one row: pixel k = lg -> (row s>>2, column 4(s&3) + lg)
+        const int col = (wave * 16 + l15 + 16 * lg) & 63;
+#pragma unroll 4
+        for (int s = 0; s < TH * 4; ++s) {
+          const int r = s >> 2, c = 4 * (s & 3) + lg;
+          const float av = dzc[(r * 16 + c) * PA + col];
+          const float* pb = pc + (r * PW + c) * 3;
+          acc0 = mfma_f32_16x16x4(av, pb[off0], acc0);
+          acc1 = mfma_f32_16x16x4(av, off1 >= 0 ? pb[off1] : ones27, acc1);
+        }
+      }
+    }
+    if (more) {
+      __syncthreads();                            // every wave is done reading the image the next tile overwrites
+      commit_tile();
     }
     __syncthreads();
-    if (!active) continue;
-    if constexpr (sizeof(T) == 2) {
-      // K step = 32 pixels = tile rows 2s, 2s+1; lane group lg owns pixels 8lg..8lg+7: row 2s + (lg>>1), cols 8(lg&1)+e
-      const int qrow = l15 >> 2, qch = (l15 & 3) * 4;
-#pragma unroll
-      for (int s = 0; s < TH / 2; ++s) {
-        const int r = 2 * s + (lg >> 1), c0 = 8 * (lg & 1);
-        const T* pa = dzt + (r * 16 + c0 + qrow) * PA + wave * 16 + qch;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(FSR_LDS_PTR(s16x4, pa));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(FSR_LDS_PTR(s16x4, pa + 4 * PA));
-        const s16x8 af = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        const float* pb = patch + (r * PW + c0) * 3;
-        float b0[8], b1[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          b0[e] = pb[e * 3 + off0];
-          b1[e] = off1 >= 0 ? pb[e * 3 + off1] : ones27;
-        }
-        const s16x8 bf0 = __builtin_bit_cast(s16x8, (u32x4){pack2<T>(b0[0], b0[1]), pack2<T>(b0[2], b0[3]),
-                                                           pack2<T>(b0[4], b0[5]), pack2<T>(b0[6], b0[7])});
-        const s16x8 bf1 = __builtin_bit_cast(s16x8, (u32x4){pack2<T>(b1[0], b1[1]), pack2<T>(b1[2], b1[3]),
-                                                           pack2<T>(b1[4], b1[5]), pack2<T>(b1[6], b1[7])});
-        acc0 = mfma16<T>(af, bf0, acc0);
-        acc1 = mfma16<T>(af, bf1, acc1);
-      }
-    } else {
-      // K step = 4 pixels of one row: pixel k = lg -> (row s>>2, column 4(s&3) + lg)
-#pragma unroll 4
-      for (int s = 0; s < TH * 4; ++s) {
-        const int r = s >> 2, c = 4 * (s & 3) + lg;
-        const float av = dzt[(r * 16 + c) * PA + wave * 16 + l15];
-        const float* pb = patch + (r * PW + c) * 3;
-        acc0 = mfma_f32_16x16x4(av, pb[off0], acc0);
-        acc1 = mfma_f32_16x16x4(av, off1 >= 0 ? pb[off1] : ones27, acc1);
-      }
-    }
   }
   if (!active) return;
   // D layout: lane column = patch column (l15 / 16 + l15), rows 4*lg + r = output channel inside the wave's tile
@@ -519,7 +637,7 @@ static int c3_wgrad_slabs(int n, int h, int w, int* tiles_x, int* tiles_y, int* 
   *tiles_x = (w + 15) / 16;
   *tiles_y = (h + 7) / 8;
   const long long ntiles = (long long)*tiles_x * *tiles_y * n;
-  long long want = 1024;                          // bandwidth-bound: four workgroups per CU in flight
+  long long want = 1024;                          // bandwidth-bound: four workgroups per CU in flight (what the f32 / x3 LDS image lets fit)
   if (want > ntiles) want = ntiles;
   *per = (int)((ntiles + want - 1) / want);
   return (int)((ntiles + *per - 1) / *per);
