@@ -19,8 +19,9 @@ PACK_FWD, PACK_FWD_PS, PACK_DGRAD, PACK_DGRAD_PS = 0, 1, 2, 3
 OUT_DTYPE, OUT_F32, OUT_U8, OUT_I420 = 0, 1, 2, 3
 YUV_BT601, YUV_BT709 = 0, 1                 # fsr_conv_desc.yuv_matrix, fsr_i420_to_image
 SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_image's input
+CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr_*_yuv entry points
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
@@ -77,6 +78,9 @@ SIGNATURES = {
     "fsr_i420_to_image_deep": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_image_to_i420": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "fsr_resample_image_i420_deep": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_yuv_to_image": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "fsr_image_to_yuv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_resample_image_yuv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "fsr_resample_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "fsr_pack_conv3x3_c3": (c_int, [c_int, P, c_int, P, c_int, P]),
     "fsr_tanh_bwd_image": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, c_int, P, P, P, P]),

@@ -503,6 +503,133 @@ __global__ __launch_bounds__(256) void image_to_i420_kernel(const float* __restr
   }
 }
 
+// 4:2:2 / 4:4:4 frames -> float [n,h,w,3] (fsr_yuv_to_image): the decode of i420_to_image_kernel without the vertical
+// interpolation.  A thread takes 4 consecutive pixels of a row: one 4- or 8-byte Y load, per chroma plane the same (4:4:4) or the samples
+// j0 - 1 .. j0 + 2 around its two chroma columns (4:2:2, j0 = x / 2, edge clamp; luma column x reads chroma at x / 2 (mpeg2) or
+// (x - 1/2) / 2 (jpeg), linear), and three 16-byte stores.  Rows of odd-width frames are not aligned and the last unit of a row may hold
+// fewer than 4 pixels: narrower accesses there.  Grid-stride over the n * h * ceil(w / 4) units (< 2^31: host checked).
+template <typename S>
+__device__ __forceinline__ void load_samples4(const S* p, int cnt, float (&v)[4]) {
+  typedef typename std::conditional<sizeof(S) == 1, unsigned, u32x2>::type quad_t;
+  if (cnt == 4 && ((size_t)p & (4 * sizeof(S) - 1)) == 0) {
+    const quad_t q = *(const quad_t*)p;
+    if constexpr (sizeof(S) == 1) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = (float)((q >> (8 * i)) & 0xffu);
+    } else {
+      v[0] = (float)(q.x & 0xffffu);
+      v[1] = (float)(q.x >> 16);
+      v[2] = (float)(q.y & 0xffffu);
+      v[3] = (float)(q.y >> 16);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = i < cnt ? (float)p[i] : 0.f;
+  }
+}
+template <typename S, int CHROMA>
+__global__ __launch_bounds__(256) void yuv_to_image_kernel(const S* __restrict__ src, float* __restrict__ dst, int n, int h, int w, int mpeg2,
+                                                           int matrix, int full, int depth) {
+  const int d = sizeof(S) == 1 ? 8 : depth;
+  const int cw = CHROMA == FSR_CHROMA_444 ? w : (w + 1) >> 1;
+  const size_t plane = (size_t)h * w, cplane = (size_t)h * cw, fsamples = plane + 2 * cplane;
+  const float kr = matrix == FSR_YUV_BT709 ? 0.2126f : 0.299f, kb = matrix == FSR_YUV_BT709 ? 0.0722f : 0.114f;
+  const float kg = 1.f - kr - kb;
+  const float up = (float)(1 << (d - 8)), top = (float)((1 << d) - 1), co = 128.f * up;
+  const float ys = full ? top : 219.f * up, yo = full ? 0.f : 16.f * up, cs = full ? top : 224.f * up;
+  const unsigned wq = (unsigned)(w + 3) >> 2;
+  const unsigned units = (unsigned)n * (unsigned)h * wq;
+  for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < units; u += gridDim.x * 256u) {
+    const unsigned row = u / wq, xq = u - row * wq;
+    const unsigned img = row / (unsigned)h, y = row - img * (unsigned)h;
+    const int x = (int)xq * 4;
+    const int cnt = w - x < 4 ? w - x : 4;
+    const S* f = src + (size_t)img * fsamples;
+    float yv[4], c[2][4];
+    load_samples4(f + (size_t)y * w + x, cnt, yv);
+    if constexpr (CHROMA == FSR_CHROMA_444) {
+      load_samples4(f + plane + (size_t)y * w + x, cnt, c[0]);
+      load_samples4(f + 2 * plane + (size_t)y * w + x, cnt, c[1]);
+    } else {
+      const int j0 = x >> 1;
+      const int ja = j0 > 0 ? j0 - 1 : 0, jb = j0 + 1 < cw ? j0 + 1 : cw - 1, jc = j0 + 2 < cw ? j0 + 2 : cw - 1;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const S* q = f + plane + k * cplane + (size_t)y * cw;
+        const float s0 = (float)q[ja], s1 = (float)q[j0], s2 = (float)q[jb], s3 = (float)q[jc];
+        // (1 - fx) * left + fx * right, as i420_to_image_kernel: mpeg2 fx = 0, 1/2, 0, 1/2 from s1; jpeg fx = 3/4, 1/4, 3/4, 1/4 from s0
+        c[k][0] = mpeg2 ? s1 : 0.25f * s0 + 0.75f * s1;
+        c[k][1] = mpeg2 ? 0.5f * s1 + 0.5f * s2 : 0.75f * s1 + 0.25f * s2;
+        c[k][2] = mpeg2 ? s2 : 0.25f * s1 + 0.75f * s2;
+        c[k][3] = mpeg2 ? 0.5f * s2 + 0.5f * s3 : 0.75f * s2 + 0.25f * s3;
+      }
+    }
+    float o[12];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float ey = (yv[i] - yo) / ys, ecb = (c[0][i] - co) / cs, ecr = (c[1][i] - co) / cs;
+      const float r = ey + 2.f * (1.f - kr) * ecr, b = ey + 2.f * (1.f - kb) * ecb;
+      const float g = (ey - kr * r - kb * b) / kg;
+      o[3 * i] = 2.f * fminf(fmaxf(r, 0.f), 1.f) - 1.f;
+      o[3 * i + 1] = 2.f * fminf(fmaxf(g, 0.f), 1.f) - 1.f;
+      o[3 * i + 2] = 2.f * fminf(fmaxf(b, 0.f), 1.f) - 1.f;
+    }
+    float* p = dst + ((size_t)row * w + x) * 3;
+    if (cnt == 4 && ((size_t)p & 15) == 0) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) *(f32x4*)(p + 4 * i) = (f32x4){o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]};
+    } else if (cnt == 4 && ((size_t)p & 7) == 0) {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) *(f32x2*)(p + 2 * i) = (f32x2){o[2 * i], o[2 * i + 1]};
+    } else {
+#pragma unroll
+      for (int i = 0; i < 12; ++i)
+        if (i < 3 * cnt) p[i] = o[i];
+    }
+  }
+}
+
+// float tanh output t [n,h,w,3] -> 4:2:2 / 4:4:4 planes (fsr_image_to_yuv; the encode of DESIGN.md §6c at any depth 8..16), in the shape of
+// image_to_i420_kernel and of the resampler's planar-YUV stage: a thread owns 4 columns x 1 row -- three 16-byte loads (narrower at the end
+// of a row whose width is no multiple of 4), c = clamp((t + 1) / 2, 0, 1), then yuv_store_1x4.  4:2:2 also takes the clamped pixel of
+// column x - 1 (column 0 at the left edge); the right neighbour of its last pair is inside the unit.  No LDS, no atomics.  Grid-stride
+// over the n * h * ceil(w / 4) units (< 2^31: host checked).
+template <typename C, int CHROMA>
+__global__ __launch_bounds__(256) void image_to_yuv_kernel(const float* __restrict__ t, C* __restrict__ out, int n, int h, int w, int matrix,
+                                                           int full, int depth) {
+  const i420_coef kc = i420_coefs(matrix, full, sizeof(C) == 1 ? 8 : depth);
+  const unsigned wq = (unsigned)(w + 3) >> 2;
+  const unsigned units = (unsigned)n * (unsigned)h * wq;
+  const size_t fsamples = (size_t)h * w + 2 * ((size_t)h * (size_t)(CHROMA == FSR_CHROMA_444 ? w : w >> 1));
+  for (unsigned u = blockIdx.x * 256u + threadIdx.x; u < units; u += gridDim.x * 256u) {
+    const unsigned row = u / wq, xq = u - row * wq;
+    const unsigned img = row / (unsigned)h, y = row - img * (unsigned)h;
+    const int x = (int)xq * 4;
+    const int cnt = w - x < 4 ? w - x : 4;
+    const float* p = t + ((size_t)row * w + x) * 3;
+    float q[12], v[12], vl[3] = {0.f, 0.f, 0.f};
+    if (cnt == 4) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const f32x4_a4 e = *(const f32x4_a4*)(p + 4 * i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[4 * i + k] = e[k];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 12; ++i) q[i] = i < 3 * cnt ? p[i] : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) v[i] = fminf(fmaxf((q[i] + 1.f) / 2.f, 0.f), 1.f);
+    if constexpr (CHROMA == FSR_CHROMA_422) {
+      const float* l = x > 0 ? p - 3 : p;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) vl[k] = fminf(fmaxf((l[k] + 1.f) / 2.f, 0.f), 1.f);
+    }
+    yuv_store_1x4<C, CHROMA>(kc, v, vl, out + (size_t)img * fsamples, h, w, (int)y, x, cnt);
+  }
+}
+
 // ------------------------------------------------------------------ out = a + b (gradient accumulation of a tensor with two consumers)
 template <typename T>
 __global__ __launch_bounds__(256) void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, long long units) {
@@ -892,6 +1019,78 @@ extern "C" int fsr_image_to_i420(const float* t, int n, int h, int w, int matrix
                        (unsigned short*)out, n, h, w, matrix, full_range, depth);
   fsr_note_kernel("image_to_i420_kernel<%s>", depth == 8 ? "u8" : "u16");
   return fsr_check_launch("image_to_i420_kernel");
+}
+
+extern "C" int fsr_yuv_to_image(const uint8_t* frames, float* img, int n, int h, int w, int chroma, int siting, int matrix, int full_range,
+                                int depth, fsr_stream_t stream_) {
+  if (chroma != FSR_CHROMA_420 && chroma != FSR_CHROMA_422 && chroma != FSR_CHROMA_444)
+    return fsr_fail(-2, "fsr_yuv_to_image: unknown chroma subsampling %d", chroma);
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_yuv_to_image: depth %d is outside 8..16", depth);
+  if (depth > 8 && ((size_t)frames & 1) != 0)
+    return fsr_fail(-2, "fsr_yuv_to_image: the payloads of 16-bit samples must be 2-byte aligned");
+  if (chroma == FSR_CHROMA_420) return i420_to_image_launch("fsr_yuv_to_image", frames, img, n, h, w, siting, matrix, full_range, depth, stream_);
+  if (!frames || !img || n <= 0 || h <= 0 || w <= 0) return fsr_fail(-1, "fsr_yuv_to_image: bad argument");
+  if (chroma == FSR_CHROMA_444) siting = FSR_SITING_JPEG;   // (no interpolation: ignored)
+  if ((siting != FSR_SITING_JPEG && siting != FSR_SITING_MPEG2) || (matrix != FSR_YUV_BT601 && matrix != FSR_YUV_BT709) ||
+      (full_range != 0 && full_range != 1))
+    return fsr_fail(-2, "fsr_yuv_to_image: unknown siting %d / matrix %d / range %d", siting, matrix, full_range);
+  if ((long long)h * w >= (1LL << 31) || (long long)n * h * w >= (1LL << 31))
+    return fsr_fail(-2, "fsr_yuv_to_image: frames of 2^31 or more pixels are not supported");
+  if (((size_t)img & 3) != 0) return fsr_fail(-2, "fsr_yuv_to_image: misaligned tensor");
+  const long long units = (long long)n * h * ((w + 3) / 4);
+  long long blocks = (units + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  const int mpeg2 = siting == FSR_SITING_MPEG2 ? 1 : 0;
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (depth == 8) {
+    const unsigned char* src = (const unsigned char*)frames;
+    if (chroma == FSR_CHROMA_422)
+      hipLaunchKernelGGL((yuv_to_image_kernel<unsigned char, FSR_CHROMA_422>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, 8);
+    else
+      hipLaunchKernelGGL((yuv_to_image_kernel<unsigned char, FSR_CHROMA_444>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, 8);
+  } else {
+    const unsigned short* src = (const unsigned short*)frames;
+    if (chroma == FSR_CHROMA_422)
+      hipLaunchKernelGGL((yuv_to_image_kernel<unsigned short, FSR_CHROMA_422>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
+    else
+      hipLaunchKernelGGL((yuv_to_image_kernel<unsigned short, FSR_CHROMA_444>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
+  }
+  fsr_note_kernel("yuv_to_image_kernel<%s,%s>", depth == 8 ? "u8" : "u16", chroma == FSR_CHROMA_422 ? "422" : "444");
+  return fsr_check_launch("yuv_to_image_kernel");
+}
+
+extern "C" int fsr_image_to_yuv(const float* t, int n, int h, int w, int chroma, int matrix, int full_range, int depth, void* out,
+                                fsr_stream_t stream_) {
+  if (chroma == FSR_CHROMA_420) return fsr_image_to_i420(t, n, h, w, matrix, full_range, depth, out, stream_);
+  if (chroma != FSR_CHROMA_422 && chroma != FSR_CHROMA_444) return fsr_fail(-2, "fsr_image_to_yuv: unknown chroma subsampling %d", chroma);
+  if (!t || !out) return fsr_fail(-1, "fsr_image_to_yuv: null argument");
+  if (n <= 0 || h <= 0 || w <= 0) return fsr_fail(-2, "fsr_image_to_yuv: bad sizes (n %d, %d x %d)", n, h, w);
+  if (chroma == FSR_CHROMA_422 && (w & 1)) return fsr_fail(-2, "fsr_image_to_yuv: 4:2:2 output needs an even output width (%d)", w);
+  if ((matrix != FSR_YUV_BT601 && matrix != FSR_YUV_BT709) || (full_range != 0 && full_range != 1))
+    return fsr_fail(-2, "fsr_image_to_yuv: unknown colour matrix %d / range %d", matrix, full_range);
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_image_to_yuv: depth %d is outside 8..16", depth);
+  if ((long long)h * w >= (1LL << 31) || (long long)n * h * w >= (1LL << 31))
+    return fsr_fail(-2, "fsr_image_to_yuv: frames of 2^31 or more pixels are not supported");
+  if (((size_t)t & 3) != 0 || (depth > 8 && ((size_t)out & 1) != 0)) return fsr_fail(-2, "fsr_image_to_yuv: misaligned tensor");
+  const long long units = (long long)n * h * ((w + 3) / 4);
+  long long blocks = (units + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  const dim3 grid((unsigned)blocks), block(256);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (depth == 8) {
+    if (chroma == FSR_CHROMA_422)
+      hipLaunchKernelGGL((image_to_yuv_kernel<unsigned char, FSR_CHROMA_422>), grid, block, 0, stream, t, (unsigned char*)out, n, h, w, matrix, full_range, 8);
+    else
+      hipLaunchKernelGGL((image_to_yuv_kernel<unsigned char, FSR_CHROMA_444>), grid, block, 0, stream, t, (unsigned char*)out, n, h, w, matrix, full_range, 8);
+  } else {
+    if (chroma == FSR_CHROMA_422)
+      hipLaunchKernelGGL((image_to_yuv_kernel<unsigned short, FSR_CHROMA_422>), grid, block, 0, stream, t, (unsigned short*)out, n, h, w, matrix, full_range, depth);
+    else
+      hipLaunchKernelGGL((image_to_yuv_kernel<unsigned short, FSR_CHROMA_444>), grid, block, 0, stream, t, (unsigned short*)out, n, h, w, matrix, full_range, depth);
+  }
+  fsr_note_kernel("image_to_yuv_kernel<%s,%s>", depth == 8 ? "u8" : "u16", chroma == FSR_CHROMA_422 ? "422" : "444");
+  return fsr_check_launch("image_to_yuv_kernel");
 }
 
 extern "C" size_t fsr_tanh_bwd_scratch(void) { return (size_t)512 * 64 * 3 * sizeof(float); }

@@ -413,6 +413,51 @@ __device__ __forceinline__ void i420_store_2x4(const i420_coef& kc, const float 
   }
 }
 
+// ---- 4:2:2 and 4:4:4 planes (fsr_image_to_yuv and the resampler's planar-YUV stage).  CHROMA is FSR_CHROMA_422 or
+// FSR_CHROMA_444; Y per pixel as above (i420_pixel).
+//   yuv444_chroma: one pixel's db = B - E_Y, dr = R - E_Y -> its Cb, Cr codes
+//   yuv422_chroma: db / dr of the pixels left of, at and right of an even luma column -> the Cb, Cr codes co-sited with it (what a C422
+//                  stream declares): s = (left + right) + 2 centre, then i420_chroma's scaling s * 0.25 / (2 (1 - K))
+template <typename C>
+__device__ __forceinline__ void yuv444_chroma(const i420_coef& k, float db, float dr, C& cb, C& cr) {
+  cb = yuv_code<C>(k.co + k.cs * (db / (2.f * (1.f - k.kb))), k.cmax);
+  cr = yuv_code<C>(k.co + k.cs * (dr / (2.f * (1.f - k.kr))), k.cmax);
+}
+template <typename C>
+__device__ __forceinline__ void yuv422_chroma(const i420_coef& k, float bl, float bc, float br, float rl, float rc, float rr, C& cb, C& cr) {
+  i420_chroma(k, (bl + br) + 2.f * bc, (rl + rr) + 2.f * rc, cb, cr);
+}
+// A thread that holds 4 columns x 1 row.  v[3 c + ch]: clamped (R, G, B) in [0, 1] of row yo, column xg + c (xg a multiple of 4) of a
+// frame of oh x ow; cnt valid columns (1..4; 2 or 4 for 4:2:2, whose ow is even -- so the right neighbour of a chroma sample is always
+// a column of the same thread).  vl (4:2:2 only): the clamped (R, G, B) of column max(xg - 1, 0), the left neighbour of the first pair.
+// Planes: Y [oh][ow], then Cb and Cr [oh][ow / 2] (4:2:2) or [oh][ow] (4:4:4).
+template <typename C, int CHROMA>
+__device__ __forceinline__ void yuv_store_1x4(const i420_coef& kc, const float (&v)[12], const float (&vl)[3], C* frame, int oh, int ow,
+                                              int yo, int xg, int cnt) {
+  const size_t plane = (size_t)oh * ow;
+  C yv[4], cb[4] = {0, 0, 0, 0}, cr[4] = {0, 0, 0, 0};
+  float db[4], dr[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) yv[c] = i420_pixel<C>(kc, v[3 * c], v[3 * c + 1], v[3 * c + 2], db[c], dr[c]);
+  store_codes4(frame + (size_t)yo * ow + xg, yv, cnt);
+  if constexpr (CHROMA == FSR_CHROMA_444) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) yuv444_chroma(kc, db[c], dr[c], cb[c], cr[c]);
+    C* c0 = frame + plane + (size_t)yo * ow + xg;
+    store_codes4(c0, cb, cnt);
+    store_codes4(c0 + plane, cr, cnt);
+  } else {
+    float dbl, drl;
+    i420_pixel<C>(kc, vl[0], vl[1], vl[2], dbl, drl);
+    yuv422_chroma(kc, dbl, db[0], db[1], drl, dr[0], dr[1], cb[0], cr[0]);
+    yuv422_chroma(kc, db[1], db[2], db[3], dr[1], dr[2], dr[3], cb[1], cr[1]);
+    const size_t cw = (size_t)(ow >> 1), cplane = (size_t)oh * cw;
+    C* c0 = frame + plane + (size_t)yo * cw + (xg >> 1);
+    store_codes4(c0, cb, cnt >> 1);
+    store_codes4(c0 + cplane, cr, cnt >> 1);
+  }
+}
+
 // sum over the 64 lanes of a wave; every lane gets the total
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -13,7 +13,11 @@
 //   2. vertical pass from LDS: a thread takes 4 consecutive floats of an output row (one ds_read_b128 per tap, the row and its
 //      taps wave-uniform), converts and stores 16 bytes of floats or one dword of bytes; for I420 it takes 4 columns x 2 rows --
 //      two whole 2x2 blocks, no shuffle -- and stores a dword of Y per row and two bytes of Cb and of Cr (i420_store_2x4,
-//      fsr_common.h; fsr_resample_image_i420_deep: the same stage with 16-bit samples at depth 9..16, 8 and 4 bytes).
+//      fsr_common.h; fsr_resample_image_i420_deep: the same stage with 16-bit samples at depth 9..16, 8 and 4 bytes);
+//      for 4:2:2 / 4:4:4 planes (fsr_resample_image_yuv) it takes 4 columns x 1 row (yuv_store_1x4).  A 4:2:2 chroma sample also needs
+//      the column left of its pair: the horizontal pass of that instantiation computes a 65th column -- the tile's left neighbour,
+//      clamped at the image edge -- with three of its idle threads and stores it behind the 64 (LDS rows of 196 floats, still a
+//      multiple of 16 bytes), in the neighbouring tile's own arithmetic.
 // Every table value is clamped to the image and to the LDS window before it is used as an index: tables that are not the ones
 // the contract names give wrong pixels, never an access outside the tensors.
 #include "fsr_common.h"
@@ -25,6 +29,9 @@ constexpr int RS_TW = 64;                  // output columns of a tile
 constexpr int RS_ROWF = RS_TW * 3;         // floats of one LDS row
 constexpr int RS_LDS_BUDGET = 64 * 1024;   // bytes of dynamic LDS a workgroup may take (several workgroups per CU stay resident)
 constexpr int RS_MAX_RATIO = 8;            // supported down-scaling ratio per axis (tap rows of up to 33)
+// template kinds of the planar 4:2:2 / 4:4:4 stages, next to the FSR_OUT_* values of the public kinds
+constexpr int RS_YUV422 = 8 + FSR_CHROMA_422, RS_YUV444 = 8 + FSR_CHROMA_444;
+constexpr int rs_rowf(int kind) { return kind == RS_YUV422 ? RS_ROWF + 4 : RS_ROWF; }   // floats of one LDS row: 4:2:2 keeps a 65th column
 
 struct ResampleArgs {
   const float* t;
@@ -51,10 +58,12 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 
 // KIND: FSR_OUT_F32 / FSR_OUT_U8 / FSR_OUT_I420.  KXS = 5 / 9: rows of at most 5 (every up-scale) / 9 (down-scales up to 2: the
 // network's 4x taken to 3x or 2x of the input) horizontal taps, held in registers; KXS = 0: any tap count, read per use.
-// C (FSR_OUT_I420 only): the sample type of the planes -- unsigned char, or unsigned short for 9..16-bit samples (a.depth).
+// C (FSR_OUT_I420, RS_YUV422, RS_YUV444): the sample type of the planes -- unsigned char, or unsigned short for 9..16-bit samples (a.depth).
 template <int KIND, int KXS, typename C = unsigned char>
 __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
   HIP_DYNAMIC_SHARED(float, lds)
+  constexpr int ROWF = rs_rowf(KIND);
+  constexpr int HT = KIND == RS_YUV422 ? RS_ROWF + 3 : RS_ROWF;   // threads of the horizontal pass
   int b = blockIdx.x;
   const int tx = b % a.tiles_x;
   b /= a.tiles_x;
@@ -69,10 +78,11 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
   const int tid = threadIdx.x;
 
   // ---- 1. horizontal pass into LDS
-  if (tid < RS_ROWF) {
+  if (tid < HT) {
     const int xo = tid / 3, ch = tid - xo * 3;
-    if (xo < tw) {
-      const int xg = x0 + xo;
+    const bool left = KIND == RS_YUV422 && xo == RS_TW;   // the column left of the tile
+    if (left || xo < tw) {
+      const int xg = left ? imax(x0 - 1, 0) : x0 + xo;
       const int xs = imin(imax(a.xmin[xg], 0), a.w - 1);
       const int ks = imin(imin(a.xsize[xg], a.kx), a.w - xs);
       const float* wrow = a.wx + (size_t)xg * a.kx;
@@ -87,23 +97,23 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
 #pragma unroll
           for (int k = 0; k < KXS; ++k)
             if (k < ks) s += wk[k] * ((p[3 * k] + 1.f) / 2.f);
-          lds[row * RS_ROWF + tid] = s;
+          lds[row * ROWF + tid] = s;
         }
       } else {
         for (int row = 0; row < nrows; ++row, p += pitch) {
           float s = 0.f;
           for (int k = 0; k < ks; ++k) s += wrow[k] * ((p[3 * k] + 1.f) / 2.f);
-          lds[row * RS_ROWF + tid] = s;
+          lds[row * ROWF + tid] = s;
         }
       }
     } else {
-      for (int row = 0; row < nrows; ++row) lds[row * RS_ROWF + tid] = 0.f;   // (the 16-byte reads of the last unit of a partial tile)
+      for (int row = 0; row < nrows; ++row) lds[row * ROWF + tid] = 0.f;   // (the 16-byte reads of the last unit of a partial tile)
     }
   }
   __syncthreads();
 
   // ---- 2. vertical pass from LDS, conversion, store
-  if constexpr (KIND != FSR_OUT_I420) {
+  if constexpr (KIND == FSR_OUT_F32 || KIND == FSR_OUT_U8) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int run = tw * 3, e0 = lane * 4;
     for (int r = wave; r < th; r += 4) {
@@ -133,6 +143,44 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
         for (int i = 0; i < 4; ++i) by[i] = (unsigned char)(clamp01(acc[i]) * 255.f);
         store_codes4((unsigned char*)a.out + o, by, cnt);
       }
+    }
+  } else if constexpr (KIND == RS_YUV422 || KIND == RS_YUV444) {
+    constexpr int CHROMA = KIND - 8;
+    const i420_coef kc = i420_coefs(a.matrix, a.full, sizeof(C) == 1 ? 8 : a.depth);
+    const size_t plane = (size_t)a.oh * a.ow;
+    C* frame = (C*)a.out + (size_t)n * (plane + 2 * ((size_t)a.oh * (size_t)(CHROMA == FSR_CHROMA_444 ? a.ow : a.ow >> 1)));
+    const int nitems = th * (RS_TW / 4);
+    for (int i = tid; i < nitems; i += 256) {
+      const int r = i / (RS_TW / 4), xl = (i - r * (RS_TW / 4)) * 4;
+      if (xl >= tw) continue;
+      const int yo = y0 + r;
+      const int j0 = imax(a.ymin[yo] - r0, 0);
+      const int ks = imin(imin(a.ysize[yo], a.ky), nrows - j0);
+      const float* wrow = a.wy + (size_t)yo * a.ky;
+      const float* col = lds + j0 * ROWF + xl * 3;
+      // 4:2:2: the three floats of the column to the left end the 16 bytes in front of the lane's own, or are the row's 65th column
+      const float* lcol = lds + j0 * ROWF + (xl ? xl * 3 - 4 : RS_ROWF);
+      f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, al = a0;
+      for (int j = 0; j < ks; ++j) {
+        const float wj = wrow[j];
+        const f32x4* q = (const f32x4*)(col + j * ROWF);
+        a0 += wj * q[0];
+        a1 += wj * q[1];
+        a2 += wj * q[2];
+        if constexpr (CHROMA == FSR_CHROMA_422) al += wj * *(const f32x4*)(lcol + j * ROWF);
+      }
+      float v[12], vl[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        v[k] = clamp01(a0[k]);
+        v[4 + k] = clamp01(a1[k]);
+        v[8 + k] = clamp01(a2[k]);
+      }
+      if constexpr (CHROMA == FSR_CHROMA_422) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) vl[k] = clamp01(xl ? al[k + 1] : al[k]);
+      }
+      yuv_store_1x4<C, CHROMA>(kc, v, vl, frame, a.oh, a.ow, yo, x0 + xl, imin(4, tw - xl));
     }
   } else {
     const i420_coef kc = i420_coefs(a.matrix, a.full, sizeof(C) == 1 ? 8 : a.depth);
@@ -197,17 +245,20 @@ void launch_kind(const ResampleArgs& a, long long grid, size_t lds_bytes, hipStr
     hipLaunchKernelGGL((resample_kernel<KIND, 0, C>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
 }
 
-// depth: 8, or 9..16 for FSR_OUT_I420 planes of 16-bit samples (fsr_resample_image_i420_deep)
+// depth: 8, or 9..16 for FSR_OUT_I420 planes of 16-bit samples (fsr_resample_image_i420_deep).  chroma (FSR_OUT_I420 only): FSR_CHROMA_420,
+// or the 4:2:2 / 4:4:4 planes of fsr_resample_image_yuv
 int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
                     const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int yuv_matrix, int yuv_full_range, int depth,
-                    void* out, fsr_stream_t stream_) {
+                    void* out, fsr_stream_t stream_, int chroma = FSR_CHROMA_420) {
   if (!t || !wy || !ymin || !ysize || !wx || !xmin || !xsize || !out) return fsr_fail(-1, "fsr_resample_image: null argument");
   if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ky <= 0 || kx <= 0)
     return fsr_fail(-2, "fsr_resample_image: bad sizes (n %d, %d x %d -> %d x %d, taps %d x %d)", n, h, w, oh, ow, ky, kx);
   if (out_kind != FSR_OUT_F32 && out_kind != FSR_OUT_U8 && out_kind != FSR_OUT_I420)
     return fsr_fail(-2, "fsr_resample_image: unknown output kind %d", out_kind);
   if (out_kind == FSR_OUT_I420) {
-    if ((oh & 1) || (ow & 1)) return fsr_fail(-2, "fsr_resample_image: I420 output needs even output extents (%d x %d)", oh, ow);
+    if (chroma == FSR_CHROMA_422 && (ow & 1))
+      return fsr_fail(-2, "fsr_resample_image: 4:2:2 output needs an even output width (%d)", ow);
+    if (chroma == FSR_CHROMA_420 && ((oh & 1) || (ow & 1))) return fsr_fail(-2, "fsr_resample_image: I420 output needs even output extents (%d x %d)", oh, ow);
     if ((yuv_matrix != FSR_YUV_BT601 && yuv_matrix != FSR_YUV_BT709) || (yuv_full_range != 0 && yuv_full_range != 1))
       return fsr_fail(-2, "fsr_resample_image: I420 output: unknown colour matrix %d / range %d", yuv_matrix, yuv_full_range);
   }
@@ -216,10 +267,11 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
   if ((long long)h > (long long)RS_MAX_RATIO * oh || (long long)w > (long long)RS_MAX_RATIO * ow)
     return fsr_fail(-2, "fsr_resample_image: down-scaling ratio %.3f x %.3f (%d x %d -> %d x %d) is beyond the supported %d", (double)h / oh,
                     (double)w / ow, h, w, oh, ow, RS_MAX_RATIO);
+  const int rowf = rs_rowf(out_kind == FSR_OUT_I420 && chroma == FSR_CHROMA_422 ? RS_YUV422 : out_kind);
   int th = 32, rows = 0;
   for (;; th >>= 1) {
     rows = window_rows(h, oh, th);
-    if ((size_t)rows * RS_ROWF * sizeof(float) <= (size_t)RS_LDS_BUDGET) break;
+    if ((size_t)rows * rowf * sizeof(float) <= (size_t)RS_LDS_BUDGET) break;
     if (th == 2)
       return fsr_fail(-2, "fsr_resample_image: down-scaling ratio %.3f (%d -> %d rows): the %d source rows of a tile do not fit %d bytes of LDS",
                       (double)h / oh, h, oh, rows, RS_LDS_BUDGET);
@@ -237,9 +289,16 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
   a.depth = depth;
   const long long grid = (long long)n * a.tiles_x * a.tiles_y;
   if (grid >= (1LL << 31)) return fsr_fail(-2, "fsr_resample_image: too many tiles (%lld)", grid);
-  const size_t lds_bytes = (size_t)rows * RS_ROWF * sizeof(float);
+  const size_t lds_bytes = (size_t)rows * rowf * sizeof(float);
   hipStream_t stream = (hipStream_t)stream_;
   const char* kind = out_kind == FSR_OUT_F32 ? "f32" : (out_kind == FSR_OUT_U8 ? "u8" : "i420");
+  if (out_kind == FSR_OUT_I420 && chroma != FSR_CHROMA_420) {
+    const bool c422 = chroma == FSR_CHROMA_422;
+    if (depth == 8) c422 ? launch_kind<RS_YUV422>(a, grid, lds_bytes, stream) : launch_kind<RS_YUV444>(a, grid, lds_bytes, stream);
+    else c422 ? launch_kind<RS_YUV422, unsigned short>(a, grid, lds_bytes, stream) : launch_kind<RS_YUV444, unsigned short>(a, grid, lds_bytes, stream);
+    fsr_note_kernel("resample_kernel<%s,%d,%s>", c422 ? "yuv422" : "yuv444", kx <= 5 ? 5 : (kx <= 9 ? 9 : 0), depth == 8 ? "u8" : "u16");
+    return fsr_check_launch("resample_kernel");
+  }
   if (out_kind == FSR_OUT_F32) launch_kind<FSR_OUT_F32>(a, grid, lds_bytes, stream);
   else if (out_kind == FSR_OUT_U8) launch_kind<FSR_OUT_U8>(a, grid, lds_bytes, stream);
   else if (depth == 8) launch_kind<FSR_OUT_I420>(a, grid, lds_bytes, stream);
@@ -263,4 +322,16 @@ extern "C" int fsr_resample_image_i420_deep(const float* t, int n, int h, int w,
   if (depth < 9 || depth > 16) return fsr_fail(-2, "fsr_resample_image_i420_deep: depth %d is outside 9..16", depth);
   return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, yuv_matrix, yuv_full_range, depth, out,
                          stream_);
+}
+
+extern "C" int fsr_resample_image_yuv(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize,
+                                      int ky, const float* wx, const int* xmin, const int* xsize, int kx, int chroma, int yuv_matrix,
+                                      int yuv_full_range, int depth, void* out, fsr_stream_t stream_) {
+  if (chroma != FSR_CHROMA_420 && chroma != FSR_CHROMA_422 && chroma != FSR_CHROMA_444)
+    return fsr_fail(-2, "fsr_resample_image_yuv: unknown chroma subsampling %d", chroma);
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_resample_image_yuv: depth %d is outside 8..16", depth);
+  if (depth > 8 && ((size_t)out & 1) != 0)
+    return fsr_fail(-2, "fsr_resample_image_yuv: the payloads of 16-bit samples must be 2-byte aligned");
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, yuv_matrix, yuv_full_range, depth, out,
+                         stream_, chroma);
 }

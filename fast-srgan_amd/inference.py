@@ -16,7 +16,7 @@ import torch
 
 from .config import load_config
 from .model import Generator
-from .ops import check_depth, i420_frame_bytes
+from .ops import check_depth, i420_frame_bytes, yuv_frame_bytes
 
 parser = ArgumentParser("Real Time Image Super Resolution")
 parser.add_argument("--image_dir", default=None, required=True, type=str)
@@ -84,6 +84,7 @@ class InferencePipeline:
     only.  `run` yields results in input order.
     Video: `run_yuv420` takes I420 payloads (planar YUV 4:2:0, Generator.forward_yuv420) through the same staging, slots and
     streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W).
+    `run_yuv` is the same for 4:2:2 and 4:4:4 payloads in or out (Generator.forward_yuv).
     Output size: every run method takes out_size = (out_h, out_w) (Generator.forward_u8 / forward_yuv420: the fused resize
     after the head, captured in the same graph).  Plans of a resized output append ("size", out_h, out_w) to the key of the
     native plan, so both coexist; None or the native size IS the native plan."""
@@ -253,6 +254,33 @@ class InferencePipeline:
             key += ("depth", depth, out_depth)
         fmt = self._Format(key, (i420_frame_bytes(h, w, depth),),
                            lambda x: model.forward_yuv420(x, h, w, out_size=out_size, depth=depth, out_depth=out_depth, **colour),
+                           self._batch_for(h, w))
+        return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
+                          for f in frames), fmt)
+
+    def run_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
+                out_full_range=None, out_size=None, depth=8, out_depth=None):
+        """run_yuv420 for planar YUV of any subsampling (Generator.forward_yuv): payloads of ops.yuv_frame_bytes(h, w, chroma, depth)
+        bytes in, of out_chroma (default: chroma) at out_depth out -- the same staging, slots and graphs.  siting=None: "mpeg2" for
+        4:2:2, "jpeg" otherwise.  Plans of any pair but ("420", "420") append ("chroma", chroma, out_chroma) to run_yuv420's key."""
+        out_chroma = chroma if out_chroma is None else out_chroma
+        if siting is None:
+            siting = "mpeg2" if chroma == "422" else "jpeg"
+        if (chroma, out_chroma) == ("420", "420"):
+            return self.run_yuv420(frames, h, w, siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
+        colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
+                      out_full_range=bool(full_range if out_full_range is None else out_full_range))
+        model = self.model
+        depth = check_depth(depth)
+        out_depth = depth if out_depth is None else check_depth(out_depth)
+        out_size = self._out_size(h, w, out_size)
+        key = ("i420", h, w) + tuple(colour.values()) + (() if out_size is None else ("size",) + out_size)
+        if (depth, out_depth) != (8, 8):
+            key += ("depth", depth, out_depth)
+        key += ("chroma", chroma, out_chroma)
+        fmt = self._Format(key, (yuv_frame_bytes(h, w, chroma, depth),),
+                           lambda x: model.forward_yuv(x, h, w, chroma=chroma, out_chroma=out_chroma, out_size=out_size, depth=depth,
+                                                       out_depth=out_depth, **colour),
                            self._batch_for(h, w))
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)

@@ -146,6 +146,40 @@ class Generator(torch.nn.Module):
         with torch.no_grad():
             return self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range, depth), cfg)
 
+    def forward_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
+                    out_full_range=None, out_size=None, depth=8, out_depth=None):
+        """forward_yuv420 for planar YUV of any subsampling: `chroma` in, `out_chroma` out ("420", "422" or "444", independent of each
+        other like depth and out_depth; out_chroma defaults to chroma).  Payloads are ops.yuv_frame_bytes(h, w, chroma, depth) bytes in
+        and ops.yuv_frame_bytes(out_h, out_w, out_chroma, out_depth) out.  siting=None: "mpeg2" for 4:2:2 input (what Y4M's C422
+        declares), "jpeg" for 4:2:0; 4:4:4 has none.  The colour contract is DESIGN.md §6c.
+        out_chroma "420" routes exactly as forward_yuv420 (and with chroma "420" IS forward_yuv420).  Any other out_chroma is the float
+        head followed by ops.image_to_yuv at the native size, or by the fused resampler for an out_size (even width for "422", any
+        extents for "444") -- "444" on a 4:2:0 source keeps the chroma the head has computed."""
+        ops.chroma_code(chroma)
+        out_chroma = chroma if out_chroma is None else out_chroma
+        ops.chroma_code(out_chroma)
+        if siting is None:
+            siting = "mpeg2" if chroma == "422" else "jpeg"
+        if chroma == "420" and out_chroma == "420":
+            return self.forward_yuv420(frames, h, w, siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
+        depth = ops.check_depth(depth)
+        out_depth = depth if out_depth is None else ops.check_depth(out_depth)
+        out_matrix = out_matrix or matrix
+        out_full = bool(full_range if out_full_range is None else out_full_range)
+        native = self._native_size(h, w, out_size)
+        with torch.no_grad():
+            x = ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth)
+            if out_chroma == "420" and native and out_depth == 8:
+                key = (ops.yuv_matrix_code(out_matrix), int(out_full))
+                cfg = self._cfg_head_i420.get(key)
+                if cfg is None:
+                    cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
+                return self._forward(x, cfg)
+            t = self._forward(x, self._cfg_head).permute(0, 2, 3, 1)
+            if native:
+                return ops.image_to_yuv(t, out_chroma, out_matrix, out_full, out_depth)
+            return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth, out_chroma)
+
     def forward(self, x):
         return self._forward(x, self._cfg_head)
 

@@ -1,4 +1,4 @@
-"""`python video.py --input IN --output OUT`: super-resolution of a YUV4MPEG2 (Y4M) stream of I420 frames.
+"""`python video.py --input IN --output OUT`: super-resolution of a YUV4MPEG2 (Y4M) stream of planar YUV frames.
 
     ffmpeg -i in.mp4 -f yuv4mpegpipe - | python video.py --input - --output - | ffmpeg -i - -c:v libx264 out.mp4
 
@@ -16,6 +16,12 @@ sources) are read as they are -- 2 bytes per sample, little-endian -- and `--out
 input's by default: `--out_depth 10` on an 8-bit source keeps the precision of the float head that 256 levels throw away.
 `C420pN` cannot declare a chroma siting; `--siting mpeg2` says what the stream cannot (HD sources are normally left-sited).
 
+4:2:2 and 4:4:4 streams (`C422`, `C444`, `C422p10`, `C444p10` ...: mezzanine and camera material, screen captures) are read as they
+are, and `--out_chroma {420,422,444}` picks the subsampling of the output, the input's by default: `--out_chroma 444` on a 4:2:0 source
+keeps the chroma samples the network has computed, which a 4:2:0 output averages away.  `--size` must be even in both extents for
+4:2:0, in the width for 4:2:2, and may be anything for 4:4:4 (an odd `--size` needs `--out_chroma` spelled out: it is checked before the
+stream is opened).  A `C422` stream is co-sited horizontally ("mpeg2"); `--siting jpeg` overrides that too.
+
 Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
 stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
 device batch at a time: a stream of any length passes through a pipe.
@@ -26,10 +32,11 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from .ops import check_depth, i420_frame_bytes
+from .ops import check_depth, i420_frame_bytes, yuv_frame_bytes
 
 MATRICES = ("bt601", "bt709")
 SITINGS = ("jpeg", "mpeg2")
+CHROMAS = ("420", "422", "444")
 
 
 class Y4MError(ValueError):
@@ -43,15 +50,24 @@ _REJECTED_C = ("420paldv", "411", "422", "444", "444alpha", "mono")
 
 class Y4MReader:
     """Streaming reader: parses the stream header on construction, then `frames()` yields one uint8 payload
-    (i420_frame_bytes(height, width, depth) bytes, a numpy array) per FRAME, reading only that frame from the file.
+    (yuv_frame_bytes(height, width, chroma, depth) bytes, a numpy array) per FRAME, reading only that frame from the file.
     max_depth: the deepest samples the caller takes.  The default, 8, refuses `C420pN` streams: their payloads are 16-bit
     little-endian samples, which a caller that indexes bytes must not be handed silently.  With max_depth >= 9, `C420pN` for
-    9 <= N <= max_depth is accepted (`.depth` = N, `.frame_bytes` twice the sample count; siting "jpeg": the tag declares none)."""
+    9 <= N <= max_depth is accepted (`.depth` = N, `.frame_bytes` twice the sample count; siting "jpeg": the tag declares none).
+    chroma: the subsamplings the caller takes.  The default, ("420",), refuses `C422` / `C444` and their `pN` forms by the same rule: a
+    caller that indexes planes must not be handed another layout silently.  With "422" / "444" in it, `C422`, `C444` and (up to
+    max_depth) `C422pN` / `C444pN` are accepted: `.chroma` says which, `.siting` is "mpeg2" for 4:2:2 (horizontally co-sited: what the
+    tag means; 4:4:4 has no siting, "jpeg" stands in)."""
 
-    def __init__(self, f, max_depth=8):
+    def __init__(self, f, max_depth=8, chroma=("420",)):
         self.f = f
         self.max_depth = check_depth(max_depth)
+        self.takes_chroma = tuple(chroma)
+        for c in self.takes_chroma:
+            if c not in CHROMAS:
+                raise ValueError("Y4MReader: chroma must be a tuple of %s, got %r" % (", ".join(CHROMAS), chroma))
         self.depth = 8
+        self.chroma = "420"
         line = f.readline()
         if not line.startswith(b"YUV4MPEG2"):
             raise Y4MError("Y4M: the stream does not start with the YUV4MPEG2 signature")
@@ -87,14 +103,28 @@ class Y4MReader:
                     self.colour_range = r.lower()
         if not self.width or not self.height or self.width <= 0 or self.height <= 0:
             raise Y4MError("Y4M: the stream header lacks the frame size (tags 'W' and 'H')")
-        self.frame_bytes = i420_frame_bytes(self.height, self.width, self.depth)
+        self.frame_bytes = yuv_frame_bytes(self.height, self.width, self.chroma, self.depth)
 
     def _colour_space(self, val):
         takes = "4:2:0 8-bit only: C420jpeg, C420mpeg2" if self.max_depth == 8 else \
             "4:2:0 only: C420jpeg, C420mpeg2, C420p9..C420p%d" % self.max_depth
+        more = [c for c in ("422", "444") if c in self.takes_chroma]
+        if more:      # (the default reader's messages stay as they were)
+            takes = "C420jpeg, C420mpeg2, %s%s" % (", ".join("C" + c for c in more), "" if self.max_depth == 8 else
+                                                   "; C420p9..C420p%d and the like" % self.max_depth)
         if val in _ACCEPTED_C:
             self.depth = 8
             return _ACCEPTED_C[val]
+        base, bits = val[:3], val[3:]
+        if base in ("422", "444") and base in self.takes_chroma and (bits == "" or (bits[0] == "p" and bits[1:].isdigit())):
+            if bits and self.max_depth == 8:
+                raise Y4MError("Y4M: colour space 'C%s' is deeper than 8 bits (this reader takes 8-bit samples only)" % val)
+            if bits and not 9 <= int(bits[1:]) <= self.max_depth:
+                raise Y4MError("Y4M: colour space 'C%s': %s bits per sample are outside what this reader takes (9..%d)"
+                               % (val, bits[1:], self.max_depth))
+            self.depth = int(bits[1:]) if bits else 8
+            self.chroma = base
+            return "mpeg2" if base == "422" else "jpeg"
         if val in _REJECTED_C:
             raise Y4MError("Y4M: colour space 'C%s' is not supported (%s)" % (val, takes))
         if "p" in val and val.split("p")[-1].isdigit():
@@ -130,13 +160,16 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes the stream header on construction (C420jpeg, or C420p<depth> for samples deeper than 8 bits; XCOLORRANGE of the
-    output range), then one FRAME per payload."""
+    """Writes the stream header on construction (C420jpeg, or C420p<depth> for samples deeper than 8 bits; chroma "422" / "444":
+    C422, C444, C422p<depth>, C444p<depth>; XCOLORRANGE of the output range), then one FRAME per payload."""
 
-    def __init__(self, f, width, height, frame_rate=None, aspect=None, interlace=None, full_range=False, depth=8):
+    def __init__(self, f, width, height, frame_rate=None, aspect=None, interlace=None, full_range=False, depth=8, chroma="420"):
         self.f = f
         self.depth = check_depth(depth)
-        self.frame_bytes = i420_frame_bytes(height, width, self.depth)
+        if chroma not in CHROMAS:
+            raise ValueError("Y4MWriter: chroma must be one of %s, got %r" % (", ".join(CHROMAS), chroma))
+        self.chroma = chroma
+        self.frame_bytes = yuv_frame_bytes(height, width, chroma, self.depth)
         tags = ["W%d" % width, "H%d" % height]
         if frame_rate is not None:
             tags.append("F" + frame_rate)
@@ -144,7 +177,8 @@ class Y4MWriter:
             tags.append("I" + interlace)
         if aspect is not None:
             tags.append("A" + aspect)
-        tags += ["C420jpeg" if self.depth == 8 else "C420p%d" % self.depth, "XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")]
+        ctag = ("C420jpeg" if chroma == "420" else "C" + chroma) if self.depth == 8 else "C%sp%d" % (chroma, self.depth)
+        tags += [ctag, "XCOLORRANGE=" + ("FULL" if full_range else "LIMITED")]
         f.write(("YUV4MPEG2 " + " ".join(tags) + "\n").encode("ascii"))
 
     def write_frame(self, payload):
@@ -155,7 +189,7 @@ class Y4MWriter:
         self.f.write(payload)
 
 
-parser = ArgumentParser("Real Time Video Super Resolution (Y4M, I420)")
+parser = ArgumentParser("Real Time Video Super Resolution (Y4M, planar YUV)")
 parser.add_argument("--input", required=True, type=str, help="Y4M stream, or - for stdin")
 parser.add_argument("--output", required=True, type=str, help="Y4M stream, or - for stdout")
 parser.add_argument("--compute_dtype", default=None, choices=["bf16", "f16", "x3", "x3v", "f32"], help="kernel precision")
@@ -165,11 +199,28 @@ parser.add_argument("--range", default="limited", choices=["limited", "full"], h
 parser.add_argument("--out_matrix", default=None, choices=MATRICES, help="colour matrix of the output (default: the input's)")
 parser.add_argument("--out_range", default=None, choices=["limited", "full"], help="output range (default: the input's)")
 parser.add_argument("--out_depth", default=None, type=int, choices=[8, 10, 12, 16], help="bits per sample of the output (default: the input's)")
+parser.add_argument("--out_chroma", default=None, choices=CHROMAS, help="chroma subsampling of the output (default: the input's)")
 parser.add_argument("--siting", default=None, choices=SITINGS,
-                    help="chroma siting of the input, overriding the stream's tag (C420pN streams cannot declare one: jpeg is assumed)")
+                    help="chroma siting of the input, overriding the stream's tag (C420pN streams cannot declare one: jpeg is assumed; "
+                         "C422 streams are mpeg2)")
 _size_flags = parser.add_mutually_exclusive_group()
-_size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="exact output size, both even (default: 4x the input)")
+_size_flags.add_argument("--size", default=None, type=str, metavar="WxH",
+                         help="exact output size (default: 4x the input): both even for 4:2:0, an even width for --out_chroma 422, anything for "
+                              "--out_chroma 444")
 _size_flags.add_argument("--scale", default=None, type=float, help="output size relative to the INPUT, rounded to even numbers")
+
+
+def video_out_size(h, w, size, scale, out_chroma):
+    """inference.resolve_out_size under the output subsampling's rule: `--size` both even for "420", an even width for "422", anything
+    for "444"; `--scale` rounds to even numbers whatever the subsampling."""
+    from .inference import resolve_out_size
+    if size is None:
+        return resolve_out_size(h, w, None, scale, even=True)
+    oh, ow = resolve_out_size(h, w, size, None, even=out_chroma == "420")
+    if out_chroma == "422" and ow % 2:
+        raise ValueError("--size %dx%d has an odd width: a YUV 4:2:2 frame holds one chroma sample per pair of pixels of a row, so the "
+                         "output width must be even" % (ow, oh))
+    return oh, ow
 
 
 def _status(msg):
@@ -180,19 +231,20 @@ def main(argv=None):
     import torch
 
     from .config import load_config
-    from .inference import InferencePipeline, load_generator, resolve_out_size
+    from .inference import InferencePipeline, load_generator
     args = parser.parse_args(argv)
-    try:
-        resolve_out_size(2, 2, args.size, args.scale, even=True)      # a malformed or odd --size fails before the stream is opened
+    try:    # a malformed or odd --size fails before the stream is opened; without --out_chroma that is 4:2:0's rule
+        video_out_size(2, 2, args.size, args.scale, args.out_chroma or "420")
     except ValueError as exc:
-        raise SystemExit("video: %s" % exc)
+        raise SystemExit("video: %s%s" % (exc, "" if args.out_chroma else " (an odd --size needs --out_chroma 422 or 444 spelled out)"))
     if not torch.cuda.is_available():
         raise SystemExit("fast-srgan_amd runs on an MI355X only: no GPU is visible")
     fin = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
     fout = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
     try:
-        reader = Y4MReader(fin, max_depth=16)
+        reader = Y4MReader(fin, max_depth=16, chroma=CHROMAS)
         siting = args.siting or reader.siting
+        chroma, out_chroma = reader.chroma, args.out_chroma or reader.chroma
         out_depth = reader.depth if args.out_depth is None else args.out_depth
         full = (reader.colour_range or args.range) == "full"
         out_full = full if args.out_range is None else args.out_range == "full"
@@ -201,19 +253,24 @@ def main(argv=None):
         model = load_generator(config, "models/model.pt", "cuda", args.compute_dtype)
         s = 2 ** len(model.upsampling)
         h, w = reader.height, reader.width
-        out_size = resolve_out_size(h, w, args.size, args.scale, even=True)
+        try:
+            out_size = video_out_size(h, w, args.size, args.scale, out_chroma)
+        except ValueError as exc:
+            raise SystemExit("video: %s" % exc)
         oh, ow = out_size or (s * h, s * w)
-        _status("video: %dx%d -> %dx%d%s, %s %s %d-bit -> %s %s %d-bit, chroma siting %s" % (
+        _status("video: %dx%d -> %dx%d%s, %s %s %d-bit -> %s %s %d-bit, chroma siting %s%s" % (
             w, h, ow, oh, "" if out_size is None else " (network %dx%d, resized)" % (s * w, s * h),
-            args.matrix, "full" if full else "limited", reader.depth, out_matrix, "full" if out_full else "limited", out_depth, siting))
+            args.matrix, "full" if full else "limited", reader.depth, out_matrix, "full" if out_full else "limited", out_depth, siting,
+            ", 4:%s:%s -> 4:%s:%s" % (chroma[1], chroma[2], out_chroma[1], out_chroma[2])))
         pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False)
         try:
-            frames_out = pipe.run_yuv420(reader.frames(), h, w, siting=siting, matrix=args.matrix, full_range=full, out_matrix=out_matrix,
-                                         out_full_range=out_full, out_size=out_size, depth=reader.depth, out_depth=out_depth)
+            frames_out = pipe.run_yuv(reader.frames(), h, w, chroma=chroma, out_chroma=out_chroma, siting=siting, matrix=args.matrix,
+                                      full_range=full, out_matrix=out_matrix, out_full_range=out_full, out_size=out_size,
+                                      depth=reader.depth, out_depth=out_depth)
         except ValueError as exc:       # a frame too large for the kernels: refused before anything is allocated or written
             raise SystemExit("video: %s" % exc)
         batch = min(args.batch, model.max_batch(h, w))      # (the pipeline has reported a batch it had to reduce)
-        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth)
+        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth, chroma=out_chroma)
         n, t0, t1 = 0, time.perf_counter(), None
         for y in frames_out:
             writer.write_frame(y)       # (a view of the pinned result buffer: written before the slot is reused)

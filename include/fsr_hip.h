@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 13
+#define FSR_ABI_VERSION 14
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
@@ -55,6 +55,7 @@ enum { FSR_PACK_FWD = 0, FSR_PACK_FWD_PS = 1, FSR_PACK_DGRAD = 2, FSR_PACK_DGRAD
 enum { FSR_OUT_DTYPE = 0, FSR_OUT_F32 = 1, FSR_OUT_U8 = 2, FSR_OUT_I420 = 3 };   /* fsr_conv_desc.out_f32 */
 enum { FSR_YUV_BT601 = 0, FSR_YUV_BT709 = 1 };             /* fsr_conv_desc.yuv_matrix, fsr_i420_to_image */
 enum { FSR_SITING_JPEG = 0, FSR_SITING_MPEG2 = 1 };        /* chroma siting of fsr_i420_to_image's input */
+enum { FSR_CHROMA_420 = 0, FSR_CHROMA_422 = 1, FSR_CHROMA_444 = 2 };   /* chroma subsampling of the fsr_*_yuv entry points */
 
 typedef void* fsr_stream_t; /* hipStream_t */
 
@@ -258,6 +259,20 @@ int fsr_i420_to_image_deep(const uint8_t* frames, float* img, int n, int h, int 
  * arithmetic and summation order of fsr_conv3x3's FSR_OUT_I420 epilogue.  One streaming kernel; n * h * w stays below 2^31. */
 int fsr_image_to_i420(const float* t, int n, int h, int w, int matrix, int full_range, int depth, void* out, fsr_stream_t stream);
 
+/* 4:2:2 and 4:4:4 (ABI 14).  A planar payload is Y [h][w], then Cb, then Cr: [(h+1)/2][(w+1)/2] each for FSR_CHROMA_420 (the
+ * I420 payload above), [h][(w+1)/2] for FSR_CHROMA_422, [h][w] for FSR_CHROMA_444; 1 byte per sample at depth 8, 2 (little-endian, the value
+ * in the low d bits) at depth 9..16, where the payloads must be 2-byte aligned.  Matrices, ranges, codes and the clamp are those of 4:2:0.
+ * fsr_yuv_to_image: n payloads (odd h and w are legal) -> float [n,h,w,3] = 2 c - 1.  4:4:4 has no interpolation and ignores `siting`;
+ *   4:2:2 interpolates chroma horizontally only, linearly with edge clamp: luma column x reads chroma at x / 2 (FSR_SITING_MPEG2, what
+ *   Y4M's C422 means) or (x - 1/2) / 2 (FSR_SITING_JPEG).  FSR_CHROMA_420 is fsr_i420_to_image / fsr_i420_to_image_deep.
+ * fsr_image_to_yuv: float tanh output t [n,h,w,3] -> n payloads of c = clamp((t + 1) / 2, 0, 1).  Y per pixel; 4:4:4: Cb, Cr per pixel;
+ *   4:2:2 (w even): chroma column j is co-sited with luma column 2j, E_C = ((d[2j-1] + d[2j+1]) + 2 d[2j]) / 4 / (2 (1 - K)) with d = B - E_Y
+ *   or R - E_Y and columns -1 and w clamped to 0 and w - 1.  FSR_CHROMA_420 is fsr_image_to_i420 (h, w even).  n * h * w stays below 2^31.
+ * Unknown chroma, depth outside 8..16, an odd 4:2:2 output width and misaligned 16-bit payloads are refused. */
+int fsr_yuv_to_image(const uint8_t* frames, float* img, int n, int h, int w, int chroma, int siting, int matrix, int full_range, int depth,
+                     fsr_stream_t stream);
+int fsr_image_to_yuv(const float* t, int n, int h, int w, int chroma, int matrix, int full_range, int depth, void* out, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ arbitrary output size: antialiased bicubic resize of the head output
  * t: the head's float tanh output [n,h,w,3] (FSR_OUT_F32 of any dtype's head) -> an oh x ow image in ONE fused kernel (horizontal pass
  * of a tile's source-row window into LDS, vertical pass from LDS, conversion, store; no global intermediate, no atomics).  The
@@ -279,6 +294,11 @@ int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, cons
 int fsr_resample_image_i420_deep(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize,
                                  int ky, const float* wx, const int* xmin, const int* xsize, int kx, int yuv_matrix, int yuv_full_range,
                                  int depth, void* out, fsr_stream_t stream);
+/* ... with planar YUV payloads of `chroma` at depth 8..16 (ABI 14; the encode of fsr_image_to_yuv on clamp(v, 0, 1), identity taps reproduce
+ * its bytes): any oh, ow for FSR_CHROMA_444, even ow for FSR_CHROMA_422; FSR_CHROMA_420 is the FSR_OUT_I420 stage above (oh, ow even). */
+int fsr_resample_image_yuv(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
+                           const float* wx, const int* xmin, const int* xsize, int kx, int chroma, int yuv_matrix, int yuv_full_range,
+                           int depth, void* out, fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ first-layer convolutions straight from the image
  * Conv2d(3 -> cout, k3, p1) of Generator.neck (model.py:75-78), Discriminator.neck (model.py:143-146) and

@@ -20,9 +20,17 @@
      -- (b) and (c) are the float head followed by the encode kernel -- then the encode kernel alone from its own events
      (ops.PROFILE_ENCODE) over its algorithmic bytes: 12 B in + 3 B out per pixel.
 
+  5. `--chroma`: 4:2:2 and 4:4:4.  360x640, batch 8, f16, every path one hipGraph, device events, interleaved round
+     by round:
+       (a) forward_yuv 420 -> 420, 8 bits (the head's I420 epilogue);   (b) 420 -> 444;   (c) 444 -> 444;   (d) 422 -> 422 at 10 bits
+     -- (b), (c), (d) are the float head followed by the encode kernel -- then the decode and encode kernels alone from their own
+     events (ops.PROFILE_YUV) over their algorithmic bytes: decode 12 B out + 3 (4:4:4) or 2 (4:2:2) B in per pixel at 8 bits, encode
+     12 B in + 3 or 2 B out.
+
     python tools/video_bench.py [--frames 2048] [--rounds 7] [--replays 20] [--modes f16,x3]
     python tools/video_bench.py --resize [--rounds 7] [--replays 20]
     python tools/video_bench.py --deep [--rounds 7] [--replays 20]
+    python tools/video_bench.py --chroma [--rounds 7] [--replays 20]
 """
 import argparse
 import importlib
@@ -206,6 +214,65 @@ def deep_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
     return med
 
 
+def chroma_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
+    dev = "cuda:0"
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+
+    def payload(chroma, depth):
+        nb = ops.yuv_frame_bytes(h, w, chroma, depth)
+        if depth == 8:
+            return torch.from_numpy(rng.integers(0, 256, size=(b, nb), dtype=np.uint8)).to(dev)
+        deep = rng.integers(0, 2 ** depth, size=(b, nb // 2), dtype=np.uint16)
+        return torch.from_numpy(np.ascontiguousarray(deep.astype("<u2")).view(np.uint8)).to(dev)
+
+    x420, x444, x422d = payload("420", 8), payload("444", 8), payload("422", d)
+    paths = [("420 -> 420, 8 bits (head epilogue)", graphed(lambda x: G.forward_yuv(x, h, w), x420)),
+             ("420 -> 444, 8 bits", graphed(lambda x: G.forward_yuv(x, h, w, out_chroma="444"), x420)),
+             ("444 -> 444, 8 bits", graphed(lambda x: G.forward_yuv(x, h, w, chroma="444"), x444)),
+             ("422 -> 422, %d bits" % d, graphed(lambda x: G.forward_yuv(x, h, w, chroma="422", depth=d), x422d))]
+    times = [[] for _ in paths]
+    for _, g in paths:
+        time_graph(g, 3)
+    for r in range(rounds):
+        order = list(range(len(paths)))
+        for i in (order if r % 2 == 0 else order[::-1]):
+            times[i].append(time_graph(paths[i][1], replays))
+    med = [statistics.median(t) for t in times]
+    for (name, _), m, t in zip(paths, med, times):
+        print("chroma      %-4s batch %d %dx%d  yuv %-36s %7.3f ms/batch  %7.1f FPS   [per-round ms %s]" % (
+            mode, b, h, w, name, 1e3 * m, b / m, " ".join("%.3f" % (1e3 * v) for v in t)), flush=True)
+    print("chroma      " + ";  ".join("%s - (a): %+.3f ms per batch (%+.2f %%)" % (paths[i][0].split(",")[0], 1e3 * (med[i] - med[0]),
+                                                                                  100.0 * (med[i] / med[0] - 1.0)) for i in (1, 2, 3)), flush=True)
+    # the decode and encode kernels alone, from their own events; the encode on a real head output
+    with torch.no_grad():
+        t = G(ops.i420_to_image(x420, h, w)).permute(0, 2, 3, 1).contiguous()
+    x444o, x422o = payload("444", 8), payload("422", 8)
+    runs = [("yuv_to_image_kernel<u8,444>", h, w, lambda: ops.yuv_to_image(x444o, h, w, "444")),
+            ("yuv_to_image_kernel<u8,422>", h, w, lambda: ops.yuv_to_image(x422o, h, w, "422")),
+            ("yuv_to_image_kernel<u16,422>", h, w, lambda: ops.yuv_to_image(x422d, h, w, "422", depth=d)),
+            ("image_to_yuv_kernel<u8,444>", 4 * h, 4 * w, lambda: ops.image_to_yuv(t, "444")),
+            ("image_to_yuv_kernel<u8,422>", 4 * h, 4 * w, lambda: ops.image_to_yuv(t, "422")),
+            ("image_to_yuv_kernel<u16,422>", 4 * h, 4 * w, lambda: ops.image_to_yuv(t, "422", depth=d))]
+    for name, kh, kw, fn in runs:
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ops.PROFILE_YUV = []
+        for _ in range(50):
+            fn()
+        torch.cuda.synchronize()
+        prof, ops.PROFILE_YUV = ops.PROFILE_YUV, None
+        ms = sorted(e0.elapsed_time(e1) for _, e0, e1, _ in prof)
+        nbytes = prof[0][3]
+        print("chroma      kernel %-30s %dx%d batch %d: median %.1f us, min %.1f us (own events, 50 launches); "
+              "%.1f MB algorithmic -> %.2f TB/s at the median" % (name, kh, kw, b, 1e3 * ms[len(ms) // 2], 1e3 * ms[0], nbytes / 1e6,
+                                                               nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
+    return med
+
+
 def end_to_end(sd, frames, mode):
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "configs"))
@@ -244,6 +311,7 @@ def main():
     ap.add_argument("--modes", default="f16,x3")
     ap.add_argument("--resize", action="store_true", help="run the arbitrary-output-size leg only")
     ap.add_argument("--deep", action="store_true", help="run the deep-sample leg only")
+    ap.add_argument("--chroma", action="store_true", help="run the 4:2:2 / 4:4:4 leg only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("video_bench needs the MI355X")
@@ -254,6 +322,9 @@ def main():
         return
     if args.deep:
         deep_leg(sd, args.rounds, args.replays)
+        return
+    if args.chroma:
+        chroma_leg(sd, args.rounds, args.replays)
         return
     model = {}
     for mode in args.modes.split(","):
