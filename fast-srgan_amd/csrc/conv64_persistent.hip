@@ -17,6 +17,7 @@
 // (144 KB + pads) does not fit next to a halo, the parity mode stays on the generic kernel.
 #include "fsr_common.h"
 #include "fsr_conv_args.h"
+#include "fsr_yuv.h"
 #include "fsr_host.h"
 
 #include <stdlib.h>

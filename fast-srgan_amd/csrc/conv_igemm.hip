@@ -36,6 +36,7 @@
 // consuming channel 4g+j).
 #include "fsr_common.h"
 #include "fsr_conv_args.h"
+#include "fsr_yuv.h"
 #include "fsr_host.h"
 
 #include <stdlib.h>

@@ -13,14 +13,14 @@
 //   2. vertical pass from LDS: a thread takes 4 consecutive floats of an output row (one ds_read_b128 per tap, the row and its
 //      taps wave-uniform), converts and stores 16 bytes of floats or one dword of bytes; for I420 it takes 4 columns x 2 rows --
 //      two whole 2x2 blocks, no shuffle -- and stores a dword of Y per row and two bytes of Cb and of Cr (i420_store_2x4,
-//      fsr_common.h; fsr_resample_image_i420_deep: the same stage with 16-bit samples at depth 9..16, 8 and 4 bytes);
+//      fsr_yuv.h; fsr_resample_image_i420_deep: the same stage with 16-bit samples at depth 9..16, 8 and 4 bytes);
 //      for 4:2:2 / 4:4:4 planes (fsr_resample_image_yuv) it takes 4 columns x 1 row (yuv_store_1x4).  A 4:2:2 chroma sample also needs
 //      the column left of its pair: the horizontal pass of that instantiation computes a 65th column -- the tile's left neighbour,
 //      clamped at the image edge -- with three of its idle threads and stores it behind the 64 (LDS rows of 196 floats, still a
 //      multiple of 16 bytes), in the neighbouring tile's own arithmetic.
 // Every table value is clamped to the image and to the LDS window before it is used as an index: tables that are not the ones
 // the contract names give wrong pixels, never an access outside the tensors.
-#include "fsr_common.h"
+#include "fsr_yuv.h"
 #include "fsr_host.h"
 
 namespace {
@@ -245,29 +245,33 @@ void launch_kind(const ResampleArgs& a, long long grid, size_t lds_bytes, hipStr
     hipLaunchKernelGGL((resample_kernel<KIND, 0, C>), dim3((unsigned)grid), dim3(256), lds_bytes, stream, a);
 }
 
-// depth: 8, or 9..16 for FSR_OUT_I420 planes of 16-bit samples (fsr_resample_image_i420_deep).  chroma (FSR_OUT_I420 only): FSR_CHROMA_420,
-// or the 4:2:2 / 4:4:4 planes of fsr_resample_image_yuv
+// The planar stages at the sample type C: 4:2:0 (FSR_OUT_I420), 4:2:2 or 4:4:4
+template <typename C>
+void launch_planar(int kind, const ResampleArgs& a, long long grid, size_t lds_bytes, hipStream_t stream) {
+  if (kind == FSR_OUT_I420) launch_kind<FSR_OUT_I420, C>(a, grid, lds_bytes, stream);
+  else if (kind == RS_YUV422) launch_kind<RS_YUV422, C>(a, grid, lds_bytes, stream);
+  else launch_kind<RS_YUV444, C>(a, grid, lds_bytes, stream);
+}
+
+// chroma, depth (FSR_OUT_I420 only; FSR_CHROMA_420 and 8 otherwise): the subsampling of the planes and their bits per sample -- 8, or 9..16
+// for 16-bit samples (fsr_resample_image_i420_deep, fsr_resample_image_yuv)
 int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
-                    const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int yuv_matrix, int yuv_full_range, int depth,
-                    void* out, fsr_stream_t stream_, int chroma = FSR_CHROMA_420) {
+                    const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int chroma, int yuv_matrix, int yuv_full_range,
+                    int depth, void* out, fsr_stream_t stream_) {
   if (!t || !wy || !ymin || !ysize || !wx || !xmin || !xsize || !out) return fsr_fail(-1, "fsr_resample_image: null argument");
   if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ky <= 0 || kx <= 0)
     return fsr_fail(-2, "fsr_resample_image: bad sizes (n %d, %d x %d -> %d x %d, taps %d x %d)", n, h, w, oh, ow, ky, kx);
   if (out_kind != FSR_OUT_F32 && out_kind != FSR_OUT_U8 && out_kind != FSR_OUT_I420)
     return fsr_fail(-2, "fsr_resample_image: unknown output kind %d", out_kind);
-  if (out_kind == FSR_OUT_I420) {
-    if (chroma == FSR_CHROMA_422 && (ow & 1))
-      return fsr_fail(-2, "fsr_resample_image: 4:2:2 output needs an even output width (%d)", ow);
-    if (chroma == FSR_CHROMA_420 && ((oh & 1) || (ow & 1))) return fsr_fail(-2, "fsr_resample_image: I420 output needs even output extents (%d x %d)", oh, ow);
-    if ((yuv_matrix != FSR_YUV_BT601 && yuv_matrix != FSR_YUV_BT709) || (yuv_full_range != 0 && yuv_full_range != 1))
-      return fsr_fail(-2, "fsr_resample_image: I420 output: unknown colour matrix %d / range %d", yuv_matrix, yuv_full_range);
-  }
+  if (out_kind == FSR_OUT_I420)
+    if (int rc = fsr_yuv_out_check("fsr_resample_image", "I420 output: ", chroma, oh, ow, yuv_matrix, yuv_full_range)) return rc;
   if ((long long)h * w >= (1LL << 31) || (long long)n * oh * ow >= (1LL << 31))
     return fsr_fail(-2, "fsr_resample_image: frames of 2^31 or more pixels are not supported");
   if ((long long)h > (long long)RS_MAX_RATIO * oh || (long long)w > (long long)RS_MAX_RATIO * ow)
     return fsr_fail(-2, "fsr_resample_image: down-scaling ratio %.3f x %.3f (%d x %d -> %d x %d) is beyond the supported %d", (double)h / oh,
                     (double)w / ow, h, w, oh, ow, RS_MAX_RATIO);
-  const int rowf = rs_rowf(out_kind == FSR_OUT_I420 && chroma == FSR_CHROMA_422 ? RS_YUV422 : out_kind);
+  const int kind = out_kind == FSR_OUT_I420 && chroma != FSR_CHROMA_420 ? 8 + chroma : out_kind;   // the kernel's KIND
+  const int rowf = rs_rowf(kind);
   int th = 32, rows = 0;
   for (;; th >>= 1) {
     rows = window_rows(h, oh, th);
@@ -291,20 +295,13 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
   if (grid >= (1LL << 31)) return fsr_fail(-2, "fsr_resample_image: too many tiles (%lld)", grid);
   const size_t lds_bytes = (size_t)rows * rowf * sizeof(float);
   hipStream_t stream = (hipStream_t)stream_;
-  const char* kind = out_kind == FSR_OUT_F32 ? "f32" : (out_kind == FSR_OUT_U8 ? "u8" : "i420");
-  if (out_kind == FSR_OUT_I420 && chroma != FSR_CHROMA_420) {
-    const bool c422 = chroma == FSR_CHROMA_422;
-    if (depth == 8) c422 ? launch_kind<RS_YUV422>(a, grid, lds_bytes, stream) : launch_kind<RS_YUV444>(a, grid, lds_bytes, stream);
-    else c422 ? launch_kind<RS_YUV422, unsigned short>(a, grid, lds_bytes, stream) : launch_kind<RS_YUV444, unsigned short>(a, grid, lds_bytes, stream);
-    fsr_note_kernel("resample_kernel<%s,%d,%s>", c422 ? "yuv422" : "yuv444", kx <= 5 ? 5 : (kx <= 9 ? 9 : 0), depth == 8 ? "u8" : "u16");
-    return fsr_check_launch("resample_kernel");
-  }
-  if (out_kind == FSR_OUT_F32) launch_kind<FSR_OUT_F32>(a, grid, lds_bytes, stream);
-  else if (out_kind == FSR_OUT_U8) launch_kind<FSR_OUT_U8>(a, grid, lds_bytes, stream);
-  else if (depth == 8) launch_kind<FSR_OUT_I420>(a, grid, lds_bytes, stream);
-  else launch_kind<FSR_OUT_I420, unsigned short>(a, grid, lds_bytes, stream);
-  if (depth == 8) fsr_note_kernel("resample_kernel<%s,%d>", kind, kx <= 5 ? 5 : (kx <= 9 ? 9 : 0));
-  else fsr_note_kernel("resample_kernel<i420,%d,u16>", kx <= 5 ? 5 : (kx <= 9 ? 9 : 0));
+  if (kind == FSR_OUT_F32) launch_kind<FSR_OUT_F32>(a, grid, lds_bytes, stream);
+  else if (kind == FSR_OUT_U8) launch_kind<FSR_OUT_U8>(a, grid, lds_bytes, stream);
+  else if (depth == 8) launch_planar<unsigned char>(kind, a, grid, lds_bytes, stream);
+  else launch_planar<unsigned short>(kind, a, grid, lds_bytes, stream);
+  const char* name = kind == FSR_OUT_F32 ? "f32" : kind == FSR_OUT_U8 ? "u8" : kind == FSR_OUT_I420 ? "i420" : kind == RS_YUV422 ? "yuv422" : "yuv444";
+  // the sample type: named for 16-bit samples, and for the 4:2:2 / 4:4:4 planes at either
+  fsr_note_kernel("resample_kernel<%s,%d%s>", name, kx <= 5 ? 5 : (kx <= 9 ? 9 : 0), depth != 8 ? ",u16" : (kind > FSR_OUT_I420 ? ",u8" : ""));
   return fsr_check_launch("resample_kernel");
 }
 
@@ -313,15 +310,15 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
 extern "C" int fsr_resample_image(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin,
                                   const int* ysize, int ky, const float* wx, const int* xmin, const int* xsize, int kx, int out_kind,
                                   int yuv_matrix, int yuv_full_range, void* out, fsr_stream_t stream_) {
-  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, out_kind, yuv_matrix, yuv_full_range, 8, out, stream_);
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, out_kind, FSR_CHROMA_420, yuv_matrix, yuv_full_range, 8, out, stream_);
 }
 
 extern "C" int fsr_resample_image_i420_deep(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin,
                                             const int* ysize, int ky, const float* wx, const int* xmin, const int* xsize, int kx,
                                             int yuv_matrix, int yuv_full_range, int depth, void* out, fsr_stream_t stream_) {
   if (depth < 9 || depth > 16) return fsr_fail(-2, "fsr_resample_image_i420_deep: depth %d is outside 9..16", depth);
-  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, yuv_matrix, yuv_full_range, depth, out,
-                         stream_);
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, FSR_CHROMA_420, yuv_matrix, yuv_full_range, depth,
+                         out, stream_);
 }
 
 extern "C" int fsr_resample_image_yuv(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize,
@@ -332,6 +329,6 @@ extern "C" int fsr_resample_image_yuv(const float* t, int n, int h, int w, int o
   if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_resample_image_yuv: depth %d is outside 8..16", depth);
   if (depth > 8 && ((size_t)out & 1) != 0)
     return fsr_fail(-2, "fsr_resample_image_yuv: the payloads of 16-bit samples must be 2-byte aligned");
-  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, yuv_matrix, yuv_full_range, depth, out,
-                         stream_, chroma);
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, chroma, yuv_matrix, yuv_full_range, depth, out,
+                         stream_);
 }

@@ -16,7 +16,7 @@ import torch
 
 from .config import load_config
 from .model import Generator
-from .ops import check_depth, i420_frame_bytes, yuv_frame_bytes
+from .ops import check_depth, yuv_frame_bytes
 
 parser = ArgumentParser("Real Time Image Super Resolution")
 parser.add_argument("--image_dir", default=None, required=True, type=str)
@@ -82,10 +82,10 @@ class InferencePipeline:
                       overlapped with the next batch's compute (`depth` staging slots, each with its own graph)
     Frames are bucketed by shape; one set of graphs per (H, W), built lazily and kept for the most recently used shapes
     only.  `run` yields results in input order.
-    Video: `run_yuv420` takes I420 payloads (planar YUV 4:2:0, Generator.forward_yuv420) through the same staging, slots and
-    streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W).
-    `run_yuv` is the same for 4:2:2 and 4:4:4 payloads in or out (Generator.forward_yuv).
-    Output size: every run method takes out_size = (out_h, out_w) (Generator.forward_u8 / forward_yuv420: the fused resize
+    Video: `run_yuv` takes planar YUV payloads (4:2:0, 4:2:2 or 4:4:4 in and out, Generator.forward_yuv) through the same staging,
+    slots and streams; its plans are keyed ("i420", H, W, colour parameters), never colliding with the RGB plans' (H, W).
+    `run_yuv420` is the same under its I420 name.
+    Output size: every run method takes out_size = (out_h, out_w) (Generator.forward_u8 / forward_yuv: the fused resize
     after the head, captured in the same graph).  Plans of a resized output append ("size", out_h, out_w) to the key of the
     native plan, so both coexist; None or the native size IS the native plan."""
 
@@ -236,38 +236,18 @@ class InferencePipeline:
         slots; a ragged tail runs eagerly at its true size."""
         return self._run(frames, None, out_size)
 
-    def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
-                   out_size=None, depth=8, out_depth=None):
-        """frames: iterable of I420 payloads of h x w (uint8 arrays or bytes of ops.i420_frame_bytes(h, w, depth) each).  Yields the
-        uint8 I420 payloads of the super-resolved frames (Generator.forward_yuv420 with these colour parameters) in order,
-        batched and pipelined exactly as `run`.  out_size = (out_h, out_w), both even: payloads of that size.  depth / out_depth
-        (8..16, out_depth defaults to depth): bits per sample in and out; payloads deeper than 8 bits are 2 bytes per sample and
-        still travel as uint8 arrays.  Plans of any pair but (8, 8) append ("depth", depth, out_depth) to the key."""
-        colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
-                      out_full_range=bool(full_range if out_full_range is None else out_full_range))
-        model = self.model
-        depth = check_depth(depth)
-        out_depth = depth if out_depth is None else check_depth(out_depth)
-        out_size = self._out_size(h, w, out_size)
-        key = ("i420", h, w) + tuple(colour.values()) + (() if out_size is None else ("size",) + out_size)
-        if (depth, out_depth) != (8, 8):
-            key += ("depth", depth, out_depth)
-        fmt = self._Format(key, (i420_frame_bytes(h, w, depth),),
-                           lambda x: model.forward_yuv420(x, h, w, out_size=out_size, depth=depth, out_depth=out_depth, **colour),
-                           self._batch_for(h, w))
-        return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
-                          for f in frames), fmt)
-
     def run_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
                 out_full_range=None, out_size=None, depth=8, out_depth=None):
-        """run_yuv420 for planar YUV of any subsampling (Generator.forward_yuv): payloads of ops.yuv_frame_bytes(h, w, chroma, depth)
-        bytes in, of out_chroma (default: chroma) at out_depth out -- the same staging, slots and graphs.  siting=None: "mpeg2" for
-        4:2:2, "jpeg" otherwise.  Plans of any pair but ("420", "420") append ("chroma", chroma, out_chroma) to run_yuv420's key."""
+        """frames: iterable of planar YUV payloads of h x w (uint8 arrays or bytes of ops.yuv_frame_bytes(h, w, chroma, depth) each).
+        Yields the uint8 payloads of the super-resolved frames, of out_chroma (default: chroma) at out_depth (Generator.forward_yuv with
+        these colour parameters), in order, batched and pipelined exactly as `run`.  siting=None: "mpeg2" for 4:2:2, "jpeg" otherwise.
+        out_size = (out_h, out_w): payloads of that size.  depth / out_depth (8..16, out_depth defaults to depth): bits per sample in and
+        out; payloads deeper than 8 bits are 2 bytes per sample and still travel as uint8 arrays.
+        Plan keys: ("i420", h, w, colour parameters), then ("size", out_h, out_w) for a resized output, ("depth", depth, out_depth) for any
+        pair but (8, 8) and ("chroma", chroma, out_chroma) for any pair but ("420", "420")."""
         out_chroma = chroma if out_chroma is None else out_chroma
         if siting is None:
             siting = "mpeg2" if chroma == "422" else "jpeg"
-        if (chroma, out_chroma) == ("420", "420"):
-            return self.run_yuv420(frames, h, w, siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
         colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
                       out_full_range=bool(full_range if out_full_range is None else out_full_range))
         model = self.model
@@ -277,13 +257,19 @@ class InferencePipeline:
         key = ("i420", h, w) + tuple(colour.values()) + (() if out_size is None else ("size",) + out_size)
         if (depth, out_depth) != (8, 8):
             key += ("depth", depth, out_depth)
-        key += ("chroma", chroma, out_chroma)
+        if (chroma, out_chroma) != ("420", "420"):
+            key += ("chroma", chroma, out_chroma)
         fmt = self._Format(key, (yuv_frame_bytes(h, w, chroma, depth),),
                            lambda x: model.forward_yuv(x, h, w, chroma=chroma, out_chroma=out_chroma, out_size=out_size, depth=depth,
                                                        out_depth=out_depth, **colour),
                            self._batch_for(h, w))
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)
+
+    def run_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
+                   out_size=None, depth=8, out_depth=None):
+        """run_yuv for I420 payloads in and out."""
+        return self.run_yuv(frames, h, w, "420", "420", siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
 
     def _run(self, frames, fmt, out_size=None):
         it = iter(frames)

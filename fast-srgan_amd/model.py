@@ -114,71 +114,53 @@ class Generator(torch.nn.Module):
         nf = self.neck[0].out_channels
         return (2 ** 31 - 1) // (int(h) * int(w) * nf * 4 ** len(self.upsampling))
 
-    def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
-                       out_size=None, depth=8, out_depth=None):
-        """Video inference on planar YUV 4:2:0 frames: (N, bytes) uint8 I420 payloads of h x w (odd sizes legal) in, (N, bytes)
-        uint8 I420 payloads of (s h) x (s w) out, s = 2 ** n_upsample.  The input is decoded on the device (matrix "bt601" /
-        "bt709", limited or full range, chroma `siting` "jpeg" or "mpeg2") into the generator's [-1, 1] RGB; the head's epilogue
-        encodes its float tanh output to Y, Cb, Cr planes (C420jpeg siting) in the output pair (out_matrix, out_full_range),
-        which defaults to the input's.  The colour contract is DESIGN.md §6c.
-        out_size = (out_h, out_w), both even: payloads of that size instead -- the float head output is resized (antialiased
-        bicubic) and encoded by one fused kernel (ops.resample_image).  None or the native size: the head's own
-        epilogue, as before.
-        depth / out_depth (8..16; out_depth defaults to depth): bits per sample of the input / output payloads -- above 8 a
-        sample is 2 bytes, little-endian (ops.i420_frame_bytes(h, w, depth); Y4M's C420p<depth>).  The two are independent
-        (8 -> 10 keeps the precision of the float head that 8-bit codes throw away).  The head's epilogue stays 8-bit: a deeper
-        native-size output is the float head followed by ops.image_to_i420."""
-        depth = ops.check_depth(depth)
-        out_depth = depth if out_depth is None else ops.check_depth(out_depth)
-        out_matrix = out_matrix or matrix
-        out_full = bool(full_range if out_full_range is None else out_full_range)
-        key = (ops.yuv_matrix_code(out_matrix), int(out_full))
-        native = self._native_size(h, w, out_size)
-        if not native or out_depth != 8:
-            with torch.no_grad():
-                t = self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range, depth), self._cfg_head).permute(0, 2, 3, 1)
-                if native:
-                    return ops.image_to_i420(t, out_matrix, out_full, out_depth)
-                return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth)
+    def _head_i420(self, matrix, full_range):
+        """ConvCfg of the head whose epilogue stores 8-bit I420 planes in (matrix, full_range), made on first use."""
+        key = (ops.yuv_matrix_code(matrix), int(full_range))
         cfg = self._cfg_head_i420.get(key)
         if cfg is None:
             cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
-        with torch.no_grad():
-            return self._forward(ops.i420_to_image(frames, h, w, siting, matrix, full_range, depth), cfg)
+        return cfg
 
     def forward_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
                     out_full_range=None, out_size=None, depth=8, out_depth=None):
-        """forward_yuv420 for planar YUV of any subsampling: `chroma` in, `out_chroma` out ("420", "422" or "444", independent of each
-        other like depth and out_depth; out_chroma defaults to chroma).  Payloads are ops.yuv_frame_bytes(h, w, chroma, depth) bytes in
-        and ops.yuv_frame_bytes(out_h, out_w, out_chroma, out_depth) out.  siting=None: "mpeg2" for 4:2:2 input (what Y4M's C422
-        declares), "jpeg" for 4:2:0; 4:4:4 has none.  The colour contract is DESIGN.md §6c.
-        out_chroma "420" routes exactly as forward_yuv420 (and with chroma "420" IS forward_yuv420).  Any other out_chroma is the float
-        head followed by ops.image_to_yuv at the native size, or by the fused resampler for an out_size (even width for "422", any
-        extents for "444") -- "444" on a 4:2:0 source keeps the chroma the head has computed."""
+        """Video inference on planar YUV frames: (N, bytes) uint8 payloads of h x w (odd sizes legal) in, (N, bytes) uint8 payloads of
+        (s h) x (s w) out, s = 2 ** n_upsample.  `chroma` in, `out_chroma` out ("420", "422" or "444", independent of each other;
+        out_chroma defaults to chroma): payloads are ops.yuv_frame_bytes(h, w, chroma, depth) bytes in and
+        ops.yuv_frame_bytes(out_h, out_w, out_chroma, out_depth) out.  The input is decoded on the device (matrix "bt601" / "bt709",
+        limited or full range, chroma `siting` "jpeg" or "mpeg2"; None: "mpeg2" for 4:2:2 input, what Y4M's C422 declares, "jpeg" for
+        4:2:0; 4:4:4 has none) into the generator's [-1, 1] RGB; the float tanh output is encoded to Y, Cb, Cr planes (4:2:0: C420jpeg
+        siting) in the output pair (out_matrix, out_full_range), which defaults to the input's.  The colour contract is DESIGN.md §6c.
+        depth / out_depth (8..16; out_depth defaults to depth): bits per sample of the input / output payloads -- above 8 a sample is 2
+        bytes, little-endian (Y4M's C420p<depth> and its kin).  The two are independent (8 -> 10 keeps the precision of the float head
+        that 8-bit codes throw away).
+        out_size = (out_h, out_w): payloads of that size instead (both even for "420", an even width for "422", any extents for "444").
+        Routes: 8-bit "420" output at the native size (out_size None or that size) is the head's own I420 epilogue.  Anything else is the
+        float head followed by ops.image_to_yuv at the native size, or by one fused kernel that resizes (antialiased bicubic) and encodes
+        (ops.resample_image) -- "444" on a 4:2:0 source keeps the chroma the head has computed."""
         ops.chroma_code(chroma)
         out_chroma = chroma if out_chroma is None else out_chroma
         ops.chroma_code(out_chroma)
-        if siting is None:
-            siting = "mpeg2" if chroma == "422" else "jpeg"
-        if chroma == "420" and out_chroma == "420":
-            return self.forward_yuv420(frames, h, w, siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
         depth = ops.check_depth(depth)
         out_depth = depth if out_depth is None else ops.check_depth(out_depth)
         out_matrix = out_matrix or matrix
         out_full = bool(full_range if out_full_range is None else out_full_range)
         native = self._native_size(h, w, out_size)
+        epilogue = out_chroma == "420" and native and out_depth == 8
+        cfg = self._head_i420(out_matrix, out_full) if epilogue else self._cfg_head
         with torch.no_grad():
-            x = ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth)
-            if out_chroma == "420" and native and out_depth == 8:
-                key = (ops.yuv_matrix_code(out_matrix), int(out_full))
-                cfg = self._cfg_head_i420.get(key)
-                if cfg is None:
-                    cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
-                return self._forward(x, cfg)
-            t = self._forward(x, self._cfg_head).permute(0, 2, 3, 1)
+            y = self._forward(ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth), cfg)
+            if epilogue:
+                return y
+            t = y.permute(0, 2, 3, 1)
             if native:
                 return ops.image_to_yuv(t, out_chroma, out_matrix, out_full, out_depth)
             return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth, out_chroma)
+
+    def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
+                       out_size=None, depth=8, out_depth=None):
+        """forward_yuv for I420 payloads in and out."""
+        return self.forward_yuv(frames, h, w, "420", "420", siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
 
     def forward(self, x):
         return self._forward(x, self._cfg_head)

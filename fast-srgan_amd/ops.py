@@ -1116,12 +1116,6 @@ def u8_to_image(frames):
     return img.permute(0, 3, 1, 2)
 
 
-def i420_frame_bytes(h, w, depth=8):
-    """Bytes of one I420 payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) each -- one byte per sample at
-    depth 8, two (little-endian, the value in the low `depth` bits: Y4M's C420p<depth>) at depths 9..16."""
-    return (h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)) * (2 if check_depth(depth) > 8 else 1)
-
-
 def check_depth(depth, lo=8):
     """The sample depth as an int, refused outside lo..16."""
     if isinstance(depth, bool) or int(depth) != depth or not lo <= depth <= 16:
@@ -1129,8 +1123,12 @@ def check_depth(depth, lo=8):
     return int(depth)
 
 
+# ---------------------------------------------------------------------------------- planar YUV in and out
 YUV_MATRICES = {"bt601": L.YUV_BT601, "bt709": L.YUV_BT709}
 CHROMA_SITINGS = {"jpeg": L.SITING_JPEG, "mpeg2": L.SITING_MPEG2}
+CHROMAS = {"420": L.CHROMA_420, "422": L.CHROMA_422, "444": L.CHROMA_444}
+_YUV_NAMES = {"420": ("i420_to_image", "image_to_i420", "I420"), "422": ("yuv_to_image", "image_to_yuv", "4:2:2"),
+              "444": ("yuv_to_image", "image_to_yuv", "4:4:4")}      # what the messages call the decode, the encode and the frames
 
 
 def yuv_matrix_code(matrix):
@@ -1139,93 +1137,46 @@ def yuv_matrix_code(matrix):
     return YUV_MATRICES[matrix]
 
 
-def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False, depth=8):
-    """(N, i420_frame_bytes(h, w, depth)) uint8 I420 payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1 of the
-    decoded RGB; chroma upsampled bilinearly at `siting` "jpeg" (centred) or "mpeg2" (co-sited horizontally); DESIGN.md
-    "Video"), the layout u8_to_image returns.  depth 9..16: payloads of 16-bit samples (fsr_i420_to_image_deep), still a uint8 tensor."""
-    _check_dev(frames)
-    depth = check_depth(depth)
-    if siting not in CHROMA_SITINGS:
-        raise ValueError("chroma siting must be one of %s, got %r" % (sorted(CHROMA_SITINGS), siting))
-    fb = i420_frame_bytes(h, w, depth)
-    if (frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != fb or not frames.is_contiguous()):
-        raise ValueError("i420_to_image expects a contiguous (N, %d) uint8 tensor of %dx%d %d-bit I420 frames, got %s %s"
-                         % (fb, w, h, depth, frames.dtype, tuple(frames.shape)))
-    n = frames.shape[0]
-    img = torch.empty((n, h, w, 3), dtype=torch.float32, device=frames.device)
-    colour = (CHROMA_SITINGS[siting], yuv_matrix_code(matrix), int(bool(full_range)))
-    if depth == 8:
-        L.check(L.lib().fsr_i420_to_image(_p(frames), _p(img), n, h, w, *colour, _stream()), "fsr_i420_to_image")
-    else:
-        L.check(L.lib().fsr_i420_to_image_deep(_p(frames), _p(img), n, h, w, *colour, depth, _stream()), "fsr_i420_to_image_deep")
-    return img.permute(0, 3, 1, 2)
-
-
-def image_to_i420(t_nhwc, matrix="bt601", full_range=False, depth=8):
-    """The I420 encode of DESIGN.md §6c on its own (fsr_image_to_i420): contiguous float32 (N,H,W,3) tanh output, H and W even ->
-    uint8 (N, i420_frame_bytes(H, W, depth)) payloads, depth 8..16 -- what the head's FSR_OUT_I420 epilogue computes, at any depth."""
-    _check_dev(t_nhwc)
-    depth = check_depth(depth)
-    if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
-        raise ValueError("image_to_i420 expects a contiguous float32 (N,H,W,3) tensor, got %s %s" % (t_nhwc.dtype, tuple(t_nhwc.shape)))
-    n, h, w, _ = t_nhwc.shape
-    if h % 2 or w % 2:
-        raise ValueError("I420 output needs even output extents, got %d x %d" % (h, w))
-    out = torch.empty((n, i420_frame_bytes(h, w, depth)), dtype=torch.uint8, device=t_nhwc.device)
-    prof = PROFILE_ENCODE
-    if prof is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    L.check(L.lib().fsr_image_to_i420(_p(t_nhwc), n, h, w, yuv_matrix_code(matrix), int(bool(full_range)), depth, _p(out), _stream()),
-            "fsr_image_to_i420")
-    if prof is not None:
-        ev1.record()
-        prof.append((ev0, ev1, t_nhwc.numel() * 4 + out.numel()))
-    return out
-
-
-PROFILE_ENCODE = None     # a list: every image_to_i420 launch appends (start event, end event, algorithmic bytes) -- tools/video_bench.py
-
-
-# ---------------------------------------------------------------------------------- 4:2:2 and 4:4:4 (DESIGN.md §6c)
-CHROMAS = {"420": L.CHROMA_420, "422": L.CHROMA_422, "444": L.CHROMA_444}
-
-
 def chroma_code(chroma):
     if chroma not in CHROMAS:
         raise ValueError("chroma subsampling must be one of %s, got %r" % (sorted(CHROMAS), chroma))
     return CHROMAS[chroma]
 
 
+def _check_yuv_extents(chroma, h, w):
+    """The output extents a subsampling can hold: even ones for "420", an even width for "422", any for "444"."""
+    if chroma == "420" and (h % 2 or w % 2):
+        raise ValueError("I420 output needs even output extents, got %d x %d" % (h, w))
+    if chroma == "422" and w % 2:
+        raise ValueError("4:2:2 output needs an even output width, got %d" % w)
+
+
 def yuv_frame_bytes(h, w, chroma="420", depth=8):
-    """Bytes of one planar YUV payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) ("420": i420_frame_bytes),
-    h x ceil(w/2) ("422") or h x w ("444") each -- one byte per sample at depth 8, two (little-endian) at depths 9..16."""
+    """Bytes of one planar YUV payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) ("420"), h x ceil(w/2) ("422")
+    or h x w ("444") each -- one byte per sample at depth 8, two (little-endian, the value in the low `depth` bits: Y4M's C420p<depth>
+    and its kin) at depths 9..16."""
     chroma_code(chroma)
-    if chroma == "420":
-        return i420_frame_bytes(h, w, depth)
-    return (h * w + 2 * h * (w if chroma == "444" else (w + 1) // 2)) * (2 if check_depth(depth) > 8 else 1)
+    ch, cw = (h + 1) // 2 if chroma == "420" else h, w if chroma == "444" else (w + 1) // 2
+    return (h * w + 2 * ch * cw) * (2 if check_depth(depth) > 8 else 1)
 
 
 def yuv_to_image(frames, h, w, chroma="420", siting=None, matrix="bt601", full_range=False, depth=8):
-    """(N, yuv_frame_bytes(h, w, chroma, depth)) uint8 planar YUV payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer, as
-    i420_to_image (which "420" is).  "444": no interpolation, `siting` is ignored.  "422": chroma interpolated horizontally only,
-    linearly with edge clamp, at `siting` "mpeg2" (co-sited with the even luma columns: what Y4M's C422 means, and the default
-    here) or "jpeg" (centred).  siting=None is "jpeg" for "420"."""
+    """(N, yuv_frame_bytes(h, w, chroma, depth)) uint8 planar YUV payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1
+    of the decoded RGB; fsr_yuv_to_image), the layout u8_to_image returns.  depth 9..16: payloads of 16-bit samples,
+    still a uint8 tensor.  "420": chroma upsampled bilinearly at `siting` "jpeg" (centred, the default) or "mpeg2" (co-sited
+    horizontally).  "422": chroma interpolated horizontally only, linearly with edge clamp, at "mpeg2" (co-sited with the even luma
+    columns: what Y4M's C422 means, and the default) or "jpeg".  "444": no interpolation, `siting` is ignored."""
     code = chroma_code(chroma)
-    if siting is None:
-        siting = "mpeg2" if chroma == "422" else "jpeg"
-    if chroma == "420":
-        return i420_to_image(frames, h, w, siting, matrix, full_range, depth)
     _check_dev(frames)
     depth = check_depth(depth)
-    if chroma == "444":
-        siting = "jpeg"
+    if siting is None or chroma == "444":
+        siting = "mpeg2" if chroma == "422" else "jpeg"
     if siting not in CHROMA_SITINGS:
         raise ValueError("chroma siting must be one of %s, got %r" % (sorted(CHROMA_SITINGS), siting))
     fb = yuv_frame_bytes(h, w, chroma, depth)
     if (frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[1] != fb or not frames.is_contiguous()):
-        raise ValueError("yuv_to_image expects a contiguous (N, %d) uint8 tensor of %dx%d %d-bit 4:%s:%s frames, got %s %s"
-                         % (fb, w, h, depth, chroma[1], chroma[2], frames.dtype, tuple(frames.shape)))
+        raise ValueError("%s expects a contiguous (N, %d) uint8 tensor of %dx%d %d-bit %s frames, got %s %s"
+                         % (_YUV_NAMES[chroma][0], fb, w, h, depth, _YUV_NAMES[chroma][2], frames.dtype, tuple(frames.shape)))
     n = frames.shape[0]
     img = torch.empty((n, h, w, 3), dtype=torch.float32, device=frames.device)
     prof = PROFILE_YUV
@@ -1236,24 +1187,21 @@ def yuv_to_image(frames, h, w, chroma="420", siting=None, matrix="bt601", full_r
                                      int(bool(full_range)), depth, _stream()), "fsr_yuv_to_image")
     if prof is not None:
         ev1.record()
-        prof.append(("decode", ev0, ev1, img.numel() * 4 + frames.numel()))
+        prof.append(("decode", chroma, ev0, ev1, img.numel() * 4 + frames.numel()))
     return img.permute(0, 3, 1, 2)
 
 
 def image_to_yuv(t_nhwc, chroma="420", matrix="bt601", full_range=False, depth=8):
     """The planar YUV encode of DESIGN.md §6c on its own (fsr_image_to_yuv): contiguous float32 (N,H,W,3) tanh output -> uint8
-    (N, yuv_frame_bytes(H, W, chroma, depth)) payloads, depth 8..16.  "420" is image_to_i420 (H, W even); "422" needs an even W (chroma
-    co-sited with the even luma columns); "444" takes any extents."""
+    (N, yuv_frame_bytes(H, W, chroma, depth)) payloads, depth 8..16 -- for "420" what the head's FSR_OUT_I420 epilogue computes, at any
+    depth.  "420" needs even H and W; "422" an even W (chroma co-sited with the even luma columns); "444" takes any extents."""
     code = chroma_code(chroma)
-    if chroma == "420":
-        return image_to_i420(t_nhwc, matrix, full_range, depth)
     _check_dev(t_nhwc)
     depth = check_depth(depth)
     if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
-        raise ValueError("image_to_yuv expects a contiguous float32 (N,H,W,3) tensor, got %s %s" % (t_nhwc.dtype, tuple(t_nhwc.shape)))
+        raise ValueError("%s expects a contiguous float32 (N,H,W,3) tensor, got %s %s" % (_YUV_NAMES[chroma][1], t_nhwc.dtype, tuple(t_nhwc.shape)))
     n, h, w, _ = t_nhwc.shape
-    if chroma == "422" and w % 2:
-        raise ValueError("4:2:2 output needs an even output width, got %d" % w)
+    _check_yuv_extents(chroma, h, w)
     out = torch.empty((n, yuv_frame_bytes(h, w, chroma, depth)), dtype=torch.uint8, device=t_nhwc.device)
     prof = PROFILE_YUV
     if prof is not None:
@@ -1263,11 +1211,24 @@ def image_to_yuv(t_nhwc, chroma="420", matrix="bt601", full_range=False, depth=8
             "fsr_image_to_yuv")
     if prof is not None:
         ev1.record()
-        prof.append(("encode", ev0, ev1, t_nhwc.numel() * 4 + out.numel()))
+        prof.append(("encode", chroma, ev0, ev1, t_nhwc.numel() * 4 + out.numel()))
     return out
 
 
-PROFILE_YUV = None        # a list: every 4:2:2 / 4:4:4 decode / encode launch appends (what, start event, end event, algorithmic bytes)
+PROFILE_YUV = None        # a list: every decode / encode launch appends (what, chroma, start event, end event, algorithmic bytes) -- tools/video_bench.py
+
+
+# 4:2:0 under its own names
+def i420_frame_bytes(h, w, depth=8):
+    return yuv_frame_bytes(h, w, "420", depth)
+
+
+def i420_to_image(frames, h, w, siting="jpeg", matrix="bt601", full_range=False, depth=8):
+    return yuv_to_image(frames, h, w, "420", siting, matrix, full_range, depth)
+
+
+def image_to_i420(t_nhwc, matrix="bt601", full_range=False, depth=8):
+    return image_to_yuv(t_nhwc, "420", matrix, full_range, depth)
 
 
 # ---------------------------------------------------------------------------------- arbitrary output size
@@ -1297,10 +1258,9 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
       kind "f32" : float32 (N,3,out_h,out_w) VIEW of an NHWC buffer, 2 v - 1 of the resized c = (t + 1) / 2 -- what
                    F.interpolate(t, mode="bicubic", antialias=True, align_corners=False) returns;
       kind "u8"  : uint8 (N,out_h,out_w,3), (unsigned char)(clamp(v, 0, 1) * 255): forward_u8's bytes at another size;
-      kind "i420": uint8 (N, i420_frame_bytes(out_h, out_w, depth)), the I420 planes of clamp(v, 0, 1) in (matrix, full_range); even
-                   extents; depth 9..16: 16-bit samples (fsr_resample_image_i420_deep).  The other kinds take depth 8 only.
-                   chroma "422" / "444": uint8 (N, yuv_frame_bytes(out_h, out_w, chroma, depth)), the planes of image_to_yuv
-                   (fsr_resample_image_yuv); even out_w for "422", any extents for "444"."""
+      kind "i420": uint8 (N, yuv_frame_bytes(out_h, out_w, chroma, depth)), the planes of image_to_yuv for clamp(v, 0, 1) in (matrix,
+                   full_range) (fsr_resample_image_yuv): "420" needs even extents, "422" an even out_w, "444" takes any; depth 9..16:
+                   16-bit samples.  The other kinds take chroma "420" and depth 8 only."""
     _check_dev(t_nhwc)
     depth = check_depth(depth)
     ccode = chroma_code(chroma)
@@ -1316,10 +1276,8 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
     if out_h <= 0 or out_w <= 0:
         raise ValueError("resample_image needs a positive output size, got %d x %d" % (out_h, out_w))
     mcode = yuv_matrix_code(matrix) if kind == "i420" else 0
-    if kind == "i420" and chroma == "420" and (out_h % 2 or out_w % 2):
-        raise ValueError("I420 output needs even output extents, got %d x %d" % (out_h, out_w))
-    if chroma == "422" and out_w % 2:
-        raise ValueError("4:2:2 output needs an even output width, got %d" % out_w)
+    if kind == "i420":
+        _check_yuv_extents(chroma, out_h, out_w)
     n, h, w, _ = t_nhwc.shape
     wy, ymin, ysize, ky = aa_taps(h, out_h, t_nhwc.device)
     wx, xmin, xsize, kx = aa_taps(w, out_w, t_nhwc.device)
@@ -1333,16 +1291,13 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    if chroma != "420":
-        L.check(L.lib().fsr_resample_image_yuv(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize),
-                                               kx, ccode, mcode, int(bool(full_range)), depth, _p(out), _stream()), "fsr_resample_image_yuv")
-    elif depth == 8:
-        L.check(L.lib().fsr_resample_image(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx,
-                                           RESAMPLE_KINDS[kind], mcode, int(bool(full_range)), _p(out), _stream()), "fsr_resample_image")
+    taps = (_p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx)
+    if kind == "i420":
+        L.check(L.lib().fsr_resample_image_yuv(_p(t_nhwc), n, h, w, out_h, out_w, *taps, ccode, mcode, int(bool(full_range)), depth, _p(out),
+                                               _stream()), "fsr_resample_image_yuv")
     else:
-        L.check(L.lib().fsr_resample_image_i420_deep(_p(t_nhwc), n, h, w, out_h, out_w, _p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin),
-                                                     _p(xsize), kx, mcode, int(bool(full_range)), depth, _p(out), _stream()),
-                "fsr_resample_image_i420_deep")
+        L.check(L.lib().fsr_resample_image(_p(t_nhwc), n, h, w, out_h, out_w, *taps, RESAMPLE_KINDS[kind], mcode, int(bool(full_range)), _p(out),
+                                           _stream()), "fsr_resample_image")
     if prof is not None:
         ev1.record()
         prof.append((ev0, ev1, t_nhwc.numel() * 4 + out.numel() * out.element_size()))

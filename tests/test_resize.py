@@ -12,7 +12,6 @@ import io
 import os
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -21,7 +20,8 @@ import torch.nn.functional as F
 
 from backend import BACKENDS, L, ops, select
 from conftest import load_npz, sd_from
-from test_video import HEAD_KERNEL, _assert_codes_close, _frames, _stream, np_encode_i420
+from test_video import HEAD_KERNEL, _frames
+from yuv_contract import _shipped, _stream, assert_codes_close, np_encode, ns
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 video = importlib.import_module("fast-srgan_amd.video")
@@ -39,10 +39,6 @@ _id = lambda p: "%dx%d-%dx%d" % (p[0] + p[1])   # noqa: E731
 @pytest.fixture(params=BACKENDS)
 def dev(request):
     return select(request.param)
-
-
-def ns(**k):
-    return types.SimpleNamespace(**k)
 
 
 def _interp(x_nchw, size):
@@ -93,7 +89,7 @@ def test_uint8_codes(dev, pair):
     t, _, v = _case(pair)
     got = ops.resample_image(t.to(dev), *pair[1], kind="u8")
     assert got.shape == (2,) + pair[1] + (3,) and got.dtype == torch.uint8
-    _assert_codes_close(got.cpu().numpy(), _u8_codes(v), 1e-3)
+    assert_codes_close(got.cpu().numpy(), _u8_codes(v), 1e-3)
 
 
 @pytest.mark.parametrize("pair", EVEN, ids=_id)
@@ -104,8 +100,8 @@ def test_i420_codes(dev, pair):
         for full in (False, True):
             got = ops.resample_image(t.to(dev), oh, ow, kind="i420", matrix=matrix, full_range=full)
             assert got.shape == (2, ops.i420_frame_bytes(oh, ow)) and got.dtype == torch.uint8
-            want = np_encode_i420(2.0 * np.clip(v.numpy(), 0.0, 1.0) - 1.0, matrix, full)
-            _assert_codes_close(got.cpu().numpy(), want, 1e-3)
+            want = np_encode(2.0 * np.clip(v.numpy(), 0.0, 1.0) - 1.0, "420", matrix, full)
+            assert_codes_close(got.cpu().numpy(), want, 1e-3)
 
 
 def test_refusals(dev):
@@ -173,7 +169,7 @@ def test_forward_u8_and_yuv420_out_size_tiny_generator(dev, pkg):
     assert got.shape == (2, 14, 30, 3) and got.dtype == torch.uint8
     with torch.no_grad():
         t = G(ops.u8_to_image(fr))
-    _assert_codes_close(got.cpu().numpy(), _u8_codes(_resized_v(t, size)), 1e-3)
+    assert_codes_close(got.cpu().numpy(), _u8_codes(_resized_v(t, size)), 1e-3)
     # None and the native size: today's path, the head's own epilogue, the same bytes
     native = G.forward_u8(fr)
     for same in (None, (20, 28)):
@@ -188,8 +184,8 @@ def test_forward_u8_and_yuv420_out_size_tiny_generator(dev, pkg):
     assert got.shape == (2, ops.i420_frame_bytes(*size)) and got.dtype == torch.uint8
     with torch.no_grad():
         t = G(ops.i420_to_image(fy, h, w, "mpeg2", "bt709", True))
-    want = np_encode_i420(2.0 * np.clip(_resized_v(t, size), 0.0, 1.0) - 1.0, "bt601", False)
-    _assert_codes_close(got.cpu().numpy(), want, 1e-3)
+    want = np_encode(2.0 * np.clip(_resized_v(t, size), 0.0, 1.0) - 1.0, "420", "bt601", False)
+    assert_codes_close(got.cpu().numpy(), want, 1e-3)
     native = G.forward_yuv420(fy, h, w, **colour)
     for same in (None, (20, 28)):
         y = G.forward_yuv420(fy, h, w, out_size=same, **colour)
@@ -248,12 +244,6 @@ def test_y4m_writer_emits_the_resized_extents():
 
 
 # ---------------------------------------------------------------------------------------------------- GPU: shipped weights
-def _shipped(pkg, dev, cdn):
-    G = pkg.Generator(ns(n_filters=64, n_layers=8), compute_dtype=cdn)
-    G.load_state_dict(sd_from(load_npz("g_model_pt.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cdn", ["f16", "x3"])
 def test_out_size_shipped_weights_gpu(pkg, cdn, monkeypatch):
@@ -267,13 +257,13 @@ def test_out_size_shipped_weights_gpu(pkg, cdn, monkeypatch):
     assert L.lib().fsr_last_kernel().decode() == "resample_kernel<u8,9>" and got.shape == (3, 50, 84, 3)     # 92 x 148 -> 50 x 84: 9 taps
     with torch.no_grad():
         t = G(ops.u8_to_image(fr))
-    _assert_codes_close(got, _u8_codes(_resized_v(t, size)), 1e-3)
+    assert_codes_close(got, _u8_codes(_resized_v(t, size)), 1e-3)
     fy = torch.from_numpy(_frames(rng, 3, h, w)).to(dev)
     got = G.forward_yuv420(fy, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix="bt709", out_size=size).cpu().numpy()
     assert L.lib().fsr_last_kernel().decode() == "resample_kernel<i420,9>" and got.shape == (3, ops.i420_frame_bytes(*size))
     with torch.no_grad():
         t = G(ops.i420_to_image(fy, h, w, "jpeg", "bt601", False))
-    _assert_codes_close(got, np_encode_i420(2.0 * np.clip(_resized_v(t, size), 0.0, 1.0) - 1.0, "bt709", False), 1e-3)
+    assert_codes_close(got, np_encode(2.0 * np.clip(_resized_v(t, size), 0.0, 1.0) - 1.0, "420", "bt709", False), 1e-3)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """Video super-resolution: I420 (planar YUV 4:2:0) frames in and out, and the Y4M stream CLI (fast-srgan_amd/video.py).
 
-The colour contract of DESIGN.md §6c is restated here in numpy (float64) and every device path is held to it:
+The colour contract of DESIGN.md §6c is restated in numpy (float64, tests/yuv_contract.py) and every device path is held to it:
   * fsr_i420_to_image (decode + bilinear chroma upsampling at the declared siting) to 2e-6;
   * the FSR_OUT_I420 epilogues of the head kernels (conv_igemm's thin path for f32, conv64_thin_kernel's 16-bit and x3 forms)
     to the textbook codes, and, on real models, to the numpy encode of the same model's float forward() output."""
@@ -10,7 +10,6 @@ import itertools
 import os
 import subprocess
 import sys
-import types
 
 import numpy as np
 import pytest
@@ -19,83 +18,13 @@ import torch
 from backend import BACKENDS, L, ops, select
 from conftest import load_npz, sd_from
 from oracle import srgan_cpu as O
+from yuv_contract import _shipped, _stream, _tiny, assert_codes_close, np_decode, np_encode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 video = importlib.import_module("fast-srgan_amd.video")
 
-# ---------------------------------------------------------------------------------------------------- the colour contract
-KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
-
-
-def _scales(full):
-    """(Y scale, Y offset, C scale): limited Y = 16 + 219 E_Y, C = 128 + 224 E_C; full Y = 255 E_Y, C = 128 + 255 E_C."""
-    return (255.0, 0.0, 255.0) if full else (219.0, 16.0, 224.0)
-
-
-def _code(v):
-    return np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint8)
-
-
-def np_encode_i420(t, matrix="bt601", full=False):
-    """(N,3,H,W) tanh output t (H, W even) -> (N, H*W*3/2) uint8 I420: c = clamp((t+1)/2, 0, 1); Y per pixel; Cb / Cr the mean
-    of E_C over each 2x2 block (C420jpeg siting); codes floor(v + 0.5) clamped to [0, 255]."""
-    t = np.asarray(t, dtype=np.float64)
-    n, _, h, w = t.shape
-    kr, kb = KR_KB[matrix]
-    kg = 1.0 - kr - kb
-    ys, yo, cs = _scales(full)
-    c = np.clip((t + 1.0) / 2.0, 0.0, 1.0)
-    r, g, b = c[:, 0], c[:, 1], c[:, 2]
-    ey = kr * r + kg * g + kb * b
-    ecb, ecr = (b - ey) / (2.0 * (1.0 - kb)), (r - ey) / (2.0 * (1.0 - kr))
-
-    def block_mean(e):
-        return e.reshape(n, h // 2, 2, w // 2, 2).mean(axis=(2, 4))
-
-    planes = [_code(yo + ys * ey), _code(128.0 + cs * block_mean(ecb)), _code(128.0 + cs * block_mean(ecr))]
-    return np.concatenate([p.reshape(n, -1) for p in planes], axis=1)
-
-
-def np_decode_i420(frames, h, w, siting="jpeg", matrix="bt601", full=False):
-    """(N, bytes) I420 payloads -> (N,3,h,w) float64 generator input 2c - 1: chroma upsampled bilinearly with edge clamp, luma
-    pixel (y, x) reading chroma at ((y - 1/2)/2, (x - 1/2)/2) (jpeg) or ((y - 1/2)/2, x/2) (mpeg2); inverse matrix; c clamped."""
-    frames = np.asarray(frames)
-    n = frames.shape[0]
-    ch, cw = (h + 1) // 2, (w + 1) // 2
-    yp = frames[:, :h * w].reshape(n, h, w).astype(np.float64)
-    cbp = frames[:, h * w:h * w + ch * cw].reshape(n, ch, cw).astype(np.float64)
-    crp = frames[:, h * w + ch * cw:].reshape(n, ch, cw).astype(np.float64)
-    cy = (np.arange(h) - 0.5) / 2.0
-    cx = (np.arange(w) - 0.5) / 2.0 if siting == "jpeg" else np.arange(w) / 2.0
-    y0, x0 = np.floor(cy).astype(int), np.floor(cx).astype(int)
-    fy, fx = (cy - y0)[:, None], (cx - x0)[None, :]
-    ya, yb = np.clip(y0, 0, ch - 1), np.clip(y0 + 1, 0, ch - 1)
-    xa, xb = np.clip(x0, 0, cw - 1), np.clip(x0 + 1, 0, cw - 1)
-
-    def up(p):
-        top = (1 - fx) * p[:, ya][:, :, xa] + fx * p[:, ya][:, :, xb]
-        bot = (1 - fx) * p[:, yb][:, :, xa] + fx * p[:, yb][:, :, xb]
-        return (1 - fy) * top + fy * bot
-
-    kr, kb = KR_KB[matrix]
-    kg = 1.0 - kr - kb
-    ys, yo, cs = _scales(full)
-    ey, ecb, ecr = (yp - yo) / ys, (up(cbp) - 128.0) / cs, (up(crp) - 128.0) / cs
-    r = ey + 2.0 * (1.0 - kr) * ecr
-    b = ey + 2.0 * (1.0 - kb) * ecb
-    g = (ey - kr * r - kb * b) / kg
-    return 2.0 * np.clip(np.stack([r, g, b], axis=1), 0.0, 1.0) - 1.0
-
-
 def _frames(rng, n, h, w):
     return rng.integers(0, 256, size=(n, ops.i420_frame_bytes(h, w)), dtype=np.uint8)
-
-
-def _assert_codes_close(got, want, frac):
-    """Every sample within 1 code; fewer than `frac` of them differ at all (float32 against float64 rounding ties)."""
-    diff = np.abs(np.asarray(got).astype(int) - np.asarray(want).astype(int))
-    assert diff.max() <= 1, diff.max()
-    assert (diff > 0).sum() <= frac * diff.size, ((diff > 0).sum(), diff.size)
 
 
 @pytest.fixture(params=BACKENDS)
@@ -103,15 +32,7 @@ def dev(request):
     return select(request.param)
 
 
-def ns(**k):
-    return types.SimpleNamespace(**k)
-
-
 # ---------------------------------------------------------------------------------------------------- Y4M (host only)
-def _stream(header, payloads, frame_line=b"FRAME\n"):
-    return header + b"".join(frame_line + bytes(p) for p in payloads)
-
-
 def test_y4m_round_trip_tags_and_frame_parameters():
     rng = np.random.default_rng(0)
     h, w = 5, 7
@@ -196,7 +117,7 @@ def test_i420_to_image_matches_the_numpy_contract(dev, siting):
         fr = _frames(rng, 2, h, w)
         got = ops.i420_to_image(torch.from_numpy(fr).to(dev), h, w, siting, matrix, full)
         assert got.shape == (2, 3, h, w) and got.dtype == torch.float32
-        want = np_decode_i420(fr, h, w, siting, matrix, full)
+        want = np_decode(fr, h, w, "420", siting, matrix, full)
         err = float(np.abs(got.cpu().double().numpy() - want).max())
         assert err < 2e-6, (h, w, matrix, full, err)
     with pytest.raises(ValueError):
@@ -232,7 +153,7 @@ def test_i420_head_epilogue_textbook_codes(dev, cdn, cin, kernel, monkeypatch):
         for name, lo, hi, code in (("Y", 0, plane, codes[0]), ("Cb", plane, plane * 5 // 4, codes[1]),
                                    ("Cr", plane * 5 // 4, plane * 3 // 2, codes[2])):
             assert (o[:, lo:hi] == code).all(), (cdn, matrix, full, signs, name, np.unique(o[:, lo:hi]))
-        assert np.array_equal(o, np_encode_i420(np.broadcast_to(np.array(signs, float)[None, :, None, None], (n, 3, h, w)), matrix, full))
+        assert np.array_equal(o, np_encode(np.broadcast_to(np.array(signs, float)[None, :, None, None], (n, 3, h, w)), "420", matrix, full))
     # refused: odd output extents, other channel counts, tensors the epilogue does not write
     x_odd = ops.to_storage(cd, torch.randn(1, 5, 6, cin)).to(dev)
     with pytest.raises(L.FsrError, match="even output extents"):
@@ -246,10 +167,7 @@ def test_i420_head_epilogue_textbook_codes(dev, cdn, cin, kernel, monkeypatch):
 def test_forward_yuv420_small_f32_generator(dev, pkg):
     """The whole Generator.forward_yuv420 (decode kernel, network, I420 head epilogue) against the numpy encode of the same
     model's float forward() on the device-decoded frames: only float32 / float64 rounding ties may differ."""
-    z = load_npz("g_tiny.npz")
-    G = pkg.Generator(ns(n_filters=16, n_layers=1), compute_dtype="f32")
-    G.load_state_dict(sd_from(z, "sd."))
-    G.to(dev).eval()
+    G = _tiny(pkg, dev)
     rng = np.random.default_rng(3)
     h, w = 3, 5
     fr = torch.from_numpy(_frames(rng, 2, h, w)).to(dev)
@@ -258,19 +176,13 @@ def test_forward_yuv420_small_f32_generator(dev, pkg):
         assert got.dtype == torch.uint8 and got.shape == (2, ops.i420_frame_bytes(4 * h, 4 * w))
         with torch.no_grad():
             t = G(ops.i420_to_image(fr, h, w, "mpeg2", matrix, full)).cpu().numpy()
-        want = np_encode_i420(t, out_matrix or matrix, full if out_full is None else out_full)
-        _assert_codes_close(got.cpu().numpy(), want, 1e-3)
+        want = np_encode(t, "420", out_matrix or matrix, full if out_full is None else out_full)
+        assert_codes_close(got.cpu().numpy(), want, 1e-3)
     with pytest.raises(ValueError):
         G.forward_yuv420(fr, h, w, matrix="bt2020")
 
 
 # ---------------------------------------------------------------------------------------------------- GPU: shipped weights
-def _shipped(pkg, dev, cdn):
-    G = pkg.Generator(ns(n_filters=64, n_layers=8), compute_dtype=cdn)
-    G.load_state_dict(sd_from(load_npz("g_model_pt.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 HEAD_KERNEL = {"f32": "conv_igemm_kernel<f32,8,16,4,1,16,1,1,0>", "f16": "conv64_thin_kernel", "bf16": "conv64_thin_kernel",
                "x3": "conv64_thin_kernel<x3>"}
 
@@ -289,13 +201,13 @@ def test_forward_yuv420_shipped_weights_gpu(pkg, cdn, monkeypatch):
     assert got.shape == (3, ops.i420_frame_bytes(4 * h, 4 * w))
     with torch.no_grad():
         t = G(ops.i420_to_image(fr, h, w, "jpeg", "bt601", False)).cpu().numpy()
-    _assert_codes_close(got, np_encode_i420(t, "bt709", False), 1e-3)
+    assert_codes_close(got, np_encode(t, "420", "bt709", False), 1e-3)
     if cdn == "f32":
         # and against the CPU oracle on the numpy decode (host and device tanh differ by an ulp: 1 code on at most 2 %)
         sd = sd_from(load_npz("g_model_pt.npz"), "sd.")
-        x = torch.from_numpy(np_decode_i420(fr.cpu().numpy(), h, w, "jpeg", "bt601", False)).float()
-        want = np_encode_i420(O.generator_forward(sd, x).numpy(), "bt709", False)
-        _assert_codes_close(got, want, 2e-2)
+        x = torch.from_numpy(np_decode(fr.cpu().numpy(), h, w, "420", "jpeg", "bt601", False)).float()
+        want = np_encode(O.generator_forward(sd, x).numpy(), "420", "bt709", False)
+        assert_codes_close(got, want, 2e-2)
 
 
 @pytest.mark.gpu

@@ -1,6 +1,6 @@
 """Video: 4:2:2 and 4:4:4 frames in and out at 8 to 16 bits (Y4M C422, C444 and their pN forms).
 
-The contract of DESIGN.md §6c for the two formats is restated here in numpy (float64), independently of the code under test.
+The contract of DESIGN.md §6c for the two formats is restated in numpy (float64, tests/yuv_contract.py), independently of the code under test.
 Storage: planar, Y h x w, then Cb, then Cr of h x ceil(w/2) (4:2:2) or h x w (4:4:4); 1 byte per sample at depth 8, 2 little-endian
 above.  Matrices, ranges, codes at depth d and the clamp are those of 4:2:0:
   limited range: Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8);  full range: Y = (2^d - 1) E_Y, C = 2^(d-1) + (2^d - 1) E_C;
@@ -12,9 +12,6 @@ s = (d[2j-1] + d[2j+1]) + 2 d[2j] (d = B - E_Y or R - E_Y, columns -1 and w clam
 import importlib
 import io
 import os
-import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -22,110 +19,19 @@ import torch
 
 from backend import BACKENDS, L, ops, select
 from conftest import load_npz, sd_from
+from yuv_contract import (CAP, _aa_matrix, _cli, _shipped, _stream, _tiny, assert_codes_close, chroma_w, from_payload, np_decode, np_encode,
+                          ns, samples_of, to_payload)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 video = importlib.import_module("fast-srgan_amd.video")
 inference = importlib.import_module("fast-srgan_amd.inference")
-dataloader = importlib.import_module("fast-srgan_amd.dataloader")
 
-KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
 COLOURS = [(m, f) for m in ("bt601", "bt709") for f in (False, True)]
-# Share of samples that may differ (by one code) from the float64 restatement: the project's caps for float32 against float64 rounding
-# ties (tests/test_video_deep.py).  test_float32_restatement_is_inside_a_third_of_the_caps keeps the float32 arithmetic alone a factor
-# of three inside them on the inputs of test_encode_random.
-CAP = {8: 1e-3, 9: 1e-3, 10: 1e-3, 12: 1e-3, 14: 1e-2, 16: 1e-2}
 ALL3 = ("420", "422", "444")
-
-
-def _coefs(full, d, ft=np.float64):
-    """(Y scale, Y offset, C scale, C offset, top code) at depth d."""
-    up, top = ft(2 ** (d - 8)), ft(2 ** d - 1)
-    return (top, ft(0), top, ft(128) * up, top) if full else (ft(219) * up, ft(16) * up, ft(224) * up, ft(128) * up, top)
-
-
-def chroma_w(w, chroma):
-    return w if chroma == "444" else (w + 1) // 2
-
-
-def samples_of(h, w, chroma):
-    return h * w + 2 * (h if chroma != "420" else (h + 1) // 2) * chroma_w(w, chroma)
-
-
-def np_encode(t, chroma, matrix="bt601", full=False, d=8, ft=np.float64):
-    """(N,3,H,W) tanh output t -> (N, samples) integer codes of the planes at depth d, computed in `ft` in the order the contract
-    writes the sums ("420": the vertical pair first, then the two columns, as DESIGN.md §6c has it for I420)."""
-    t = np.asarray(t).astype(ft)
-    n, _, h, w = t.shape
-    kr, kb = (ft(v) for v in KR_KB[matrix])
-    kg = ft(1) - kr - kb
-    ys, yo, cs, co, top = _coefs(full, d, ft)
-    c = np.clip((t + ft(1)) / ft(2), ft(0), ft(1))
-    r, g, b = c[:, 0], c[:, 1], c[:, 2]
-    ey = kr * r + kg * g + kb * b
-
-    def sub(e, k):
-        if chroma == "444":
-            return e / (ft(2) * (ft(1) - k))
-        if chroma == "422":
-            centre = np.arange(0, w, 2)
-            left, right = np.clip(centre - 1, 0, w - 1), np.clip(centre + 1, 0, w - 1)
-            s = (e[:, :, left] + e[:, :, right]) + ft(2) * e[:, :, centre]
-        else:
-            col = e[:, 0::2, :] + e[:, 1::2, :]
-            s = col[:, :, 0::2] + col[:, :, 1::2]
-        return s * ft(0.25) / (ft(2) * (ft(1) - k))
-
-    def code(v):
-        return np.clip(np.floor(v + ft(0.5)), 0, top).astype(np.int64)
-
-    return np.concatenate([p.reshape(n, -1) for p in (code(yo + ys * ey), code(co + cs * sub(b - ey, kb)), code(co + cs * sub(r - ey, kr)))],
-                          axis=1)
-
-
-def np_decode(samples, h, w, chroma, siting="mpeg2", matrix="bt601", full=False, d=8):
-    """(N, samples) integer codes of 4:2:2 / 4:4:4 planes -> (N,3,h,w) float64 generator input 2c - 1."""
-    s = np.asarray(samples).astype(np.float64)
-    n = s.shape[0]
-    cw = chroma_w(w, chroma)
-    yp = s[:, :h * w].reshape(n, h, w)
-    cbp = s[:, h * w:h * w + h * cw].reshape(n, h, cw)
-    crp = s[:, h * w + h * cw:].reshape(n, h, cw)
-    if chroma == "422":
-        cx = np.arange(w) / 2.0 if siting == "mpeg2" else (np.arange(w) - 0.5) / 2.0
-        x0 = np.floor(cx).astype(int)
-        fx = (cx - x0)[None, None, :]
-        xa, xb = np.clip(x0, 0, cw - 1), np.clip(x0 + 1, 0, cw - 1)
-        cbp, crp = ((1 - fx) * p[:, :, xa] + fx * p[:, :, xb] for p in (cbp, crp))
-    kr, kb = KR_KB[matrix]
-    kg = 1.0 - kr - kb
-    ys, yo, cs, co, _ = _coefs(full, d)
-    ey, ecb, ecr = (yp - yo) / ys, (cbp - co) / cs, (crp - co) / cs
-    r = ey + 2.0 * (1.0 - kr) * ecr
-    b = ey + 2.0 * (1.0 - kb) * ecb
-    g = (ey - kr * r - kb * b) / kg
-    return 2.0 * np.clip(np.stack([r, g, b], axis=1), 0.0, 1.0) - 1.0
-
-
-def to_payload(codes, d):
-    codes = np.ascontiguousarray(codes)
-    return codes.astype(np.uint8) if d == 8 else np.ascontiguousarray(codes.astype("<u2")).view(np.uint8)
-
-
-def from_payload(payload, d):
-    payload = np.ascontiguousarray(np.asarray(payload))
-    return payload.astype(np.int64) if d == 8 else payload.view("<u2").astype(np.int64)
 
 
 def _rand_payload(rng, n, h, w, chroma, d):
     return to_payload(rng.integers(0, 2 ** d, size=(n, samples_of(h, w, chroma))), d)
-
-
-def assert_codes_close(got, want, frac):
-    """Every sample within 1 code; at most `frac` of them differ at all."""
-    diff = np.abs(np.asarray(got).astype(np.int64) - np.asarray(want).astype(np.int64))
-    print("codes: max difference %d, %d of %d differ (cap %g)" % (diff.max(), (diff > 0).sum(), diff.size, frac))
-    assert diff.max() <= 1, diff.max()
-    assert (diff > 0).sum() <= frac * diff.size, ((diff > 0).sum(), diff.size)
 
 
 def _kernel():
@@ -137,15 +43,7 @@ def dev(request):
     return select(request.param)
 
 
-def ns(**k):
-    return types.SimpleNamespace(**k)
-
-
 # ---------------------------------------------------------------------------------------------------- 1. Y4M (host only)
-def _stream(header, payloads):
-    return header + b"".join(b"FRAME\n" + bytes(p) for p in payloads)
-
-
 def test_y4m_reader_takes_422_and_444_only_when_asked():
     for tag in (b"C422", b"C444", b"C422p10"):
         for md in (8, 16):
@@ -423,14 +321,6 @@ def test_encode_is_the_resamplers_planar_stage_at_the_native_size(dev, chroma, s
 
 
 # ---------------------------------------------------------------------------------------------------- 6. resize
-def _aa_matrix(n_in, n_out):
-    xmin, xsize, taps, _ = dataloader.aa_bicubic_taps(n_in, n_out)
-    m = np.zeros((n_out, n_in))
-    for i in range(n_out):
-        m[i, xmin[i]:xmin[i] + xsize[i]] = taps[i, :xsize[i]].astype(np.float64)
-    return m
-
-
 def _np_resize(t_nchw, oh, ow):
     """float64 tap composition of the antialiased bicubic on c = (t + 1) / 2, clamped, back as a tanh-range tensor."""
     c = (np.asarray(t_nchw).astype(np.float64) + 1.0) / 2.0
@@ -487,12 +377,6 @@ def test_resize_refusals_and_tap_forms(dev):
 
 
 # ---------------------------------------------------------------------------------------------------- 7. the whole generator
-def _tiny(pkg, dev):
-    G = pkg.Generator(ns(n_filters=16, n_layers=1), compute_dtype="f32")
-    G.load_state_dict(sd_from(load_npz("g_tiny.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 def _rand_420(rng, n, h, w, d):
     return to_payload(rng.integers(0, 2 ** d, size=(n, samples_of(h, w, "420"))), d)
 
@@ -557,12 +441,6 @@ def test_pipeline_run_yuv_keys_and_frame_sizes(pkg):
 
 
 # ---------------------------------------------------------------------------------------------------- 8. GPU only
-def _shipped(pkg, dev, cdn):
-    G = pkg.Generator(ns(n_filters=64, n_layers=8), compute_dtype=cdn)
-    G.load_state_dict(sd_from(load_npz("g_model_pt.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cdn", ["f16", "x3"])
 def test_forward_yuv_shipped_weights_gpu(pkg, cdn, monkeypatch):
@@ -613,13 +491,6 @@ def cli_dir(tmp_path_factory):
     torch.save({"_orig_mod." + k: v for k, v in sd.items()}, d / "models" / "model.pt")
     (d / "configs" / "config.yaml").write_text("generator:\n  n_filters: 64\n  n_layers: 8\ntraining:\n  compute_dtype: f16\n")
     return d
-
-
-def _cli(cli_dir, data, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "video.py"), "--input", "-", "--output", "-", "--batch", "2"] + list(flags),
-                       input=data, capture_output=True, cwd=cli_dir, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    return r
 
 
 def _cli_model(cli_dir, dev):

@@ -1,6 +1,6 @@
 """Video: 9- to 16-bit 4:2:0 frames in and out (Y4M C420p10 and its kin), and the batch the kernels can index.
 
-The depth contract of DESIGN.md §6c is restated here in numpy (float64), independently of the code under test.  Sample depth d,
+The depth contract of DESIGN.md §6c is restated in numpy (float64, tests/yuv_contract.py), independently of the code under test.  Sample depth d,
 8 <= d <= 16; a deep payload (d > 8) has the plane order and extents of an 8-bit one, every sample 2 bytes little-endian:
   limited range: Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8);  full range: Y = (2^d - 1) E_Y, C = 2^(d-1) + (2^d - 1) E_C;
   encode: code = clamp(floor(v + 0.5), 0, 2^d - 1).
@@ -10,9 +10,6 @@ InferencePipeline.run_yuv420 and the video CLI at every pair of depths."""
 import importlib
 import io
 import os
-import subprocess
-import sys
-import types
 
 import numpy as np
 import pytest
@@ -20,108 +17,15 @@ import torch
 
 from backend import BACKENDS, L, ops, select
 from conftest import load_npz, sd_from
+from yuv_contract import (CAP, _aa_matrix, _cli, _shipped, _stream, _tiny, assert_codes_close, from_payload, np_decode, np_encode, ns,
+                          samples_of, to_payload)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 video = importlib.import_module("fast-srgan_amd.video")
 inference = importlib.import_module("fast-srgan_amd.inference")
-dataloader = importlib.import_module("fast-srgan_amd.dataloader")
-
-KR_KB = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}
-# Share of samples that may differ (by one code) from the float64 restatement.  1e-3 is the project's cap for float32 against
-# float64 rounding ties (tests/test_video.py).  Measured: the float32 restatement below ALONE, against float64, on the inputs of
-# test_encode_random (both shapes, all four matrix / range pairs: 4680 samples per depth) differs on 0 samples at d = 8 and 12, on 1
-# (0.021 %) at d = 10, on 3 (0.064 %) at d = 14 and on 10 (0.214 %) at d = 16 -- float32 resolves only 1/1024 and 1/256 of a code at
-# the top of the 14- and 16-bit ranges, so more ties fall the other way there, and the cap is 1e-2: more than three times either
-# measurement (test_float32_restatement_is_inside_the_caps keeps that true).
-CAP = {8: 1e-3, 9: 1e-3, 10: 1e-3, 12: 1e-3, 14: 1e-2, 16: 1e-2}
-
-
-def _coefs(full, d, ft=np.float64):
-    """(Y scale, Y offset, C scale, C offset, top code) at depth d."""
-    up, top = ft(2 ** (d - 8)), ft(2 ** d - 1)
-    return (top, ft(0), top, ft(128) * up, top) if full else (ft(219) * up, ft(16) * up, ft(224) * up, ft(128) * up, top)
-
-
-def np_encode(t, matrix="bt601", full=False, d=8, ft=np.float64):
-    """(N,3,H,W) tanh output t (H, W even) -> (N, samples) integer codes of the I420 planes at depth d, computed in `ft`; the
-    chroma mean is summed in the kernels' order (the vertical pair first, then the two columns)."""
-    t = np.asarray(t).astype(ft)
-    n, _, h, w = t.shape
-    kr, kb = (ft(v) for v in KR_KB[matrix])
-    kg = ft(1) - kr - kb
-    ys, yo, cs, co, top = _coefs(full, d, ft)
-    c = np.clip((t + ft(1)) / ft(2), ft(0), ft(1))
-    r, g, b = c[:, 0], c[:, 1], c[:, 2]
-    ey = kr * r + kg * g + kb * b
-
-    def block_mean(e):
-        col = e[:, 0::2, :] + e[:, 1::2, :]
-        return (col[:, :, 0::2] + col[:, :, 1::2]) * ft(0.25)
-
-    ecb, ecr = block_mean(b - ey) / (ft(2) * (ft(1) - kb)), block_mean(r - ey) / (ft(2) * (ft(1) - kr))
-
-    def code(v):
-        return np.clip(np.floor(v + ft(0.5)), 0, top).astype(np.int64)
-
-    return np.concatenate([p.reshape(n, -1) for p in (code(yo + ys * ey), code(co + cs * ecb), code(co + cs * ecr))], axis=1)
-
-
-def np_decode(samples, h, w, siting="jpeg", matrix="bt601", full=False, d=8):
-    """(N, samples) integer codes -> (N,3,h,w) float64 generator input 2c - 1: chroma upsampled bilinearly with edge clamp, luma pixel
-    (y, x) reading chroma at ((y - 1/2)/2, (x - 1/2)/2) (jpeg) or ((y - 1/2)/2, x/2) (mpeg2); inverse matrix; c clamped."""
-    s = np.asarray(samples).astype(np.float64)
-    n = s.shape[0]
-    ch, cw = (h + 1) // 2, (w + 1) // 2
-    yp = s[:, :h * w].reshape(n, h, w)
-    cbp = s[:, h * w:h * w + ch * cw].reshape(n, ch, cw)
-    crp = s[:, h * w + ch * cw:].reshape(n, ch, cw)
-    cy = (np.arange(h) - 0.5) / 2.0
-    cx = (np.arange(w) - 0.5) / 2.0 if siting == "jpeg" else np.arange(w) / 2.0
-    y0, x0 = np.floor(cy).astype(int), np.floor(cx).astype(int)
-    fy, fx = (cy - y0)[:, None], (cx - x0)[None, :]
-    ya, yb = np.clip(y0, 0, ch - 1), np.clip(y0 + 1, 0, ch - 1)
-    xa, xb = np.clip(x0, 0, cw - 1), np.clip(x0 + 1, 0, cw - 1)
-
-    def up(p):
-        top = (1 - fx) * p[:, ya][:, :, xa] + fx * p[:, ya][:, :, xb]
-        bot = (1 - fx) * p[:, yb][:, :, xa] + fx * p[:, yb][:, :, xb]
-        return (1 - fy) * top + fy * bot
-
-    kr, kb = KR_KB[matrix]
-    kg = 1.0 - kr - kb
-    ys, yo, cs, co, _ = _coefs(full, d)
-    ey, ecb, ecr = (yp - yo) / ys, (up(cbp) - co) / cs, (up(crp) - co) / cs
-    r = ey + 2.0 * (1.0 - kr) * ecr
-    b = ey + 2.0 * (1.0 - kb) * ecb
-    g = (ey - kr * r - kb * b) / kg
-    return 2.0 * np.clip(np.stack([r, g, b], axis=1), 0.0, 1.0) - 1.0
-
-
-def samples_of(h, w):
-    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
-
-
-def to_payload(codes, d):
-    """(N, samples) integer codes -> the (N, bytes) uint8 payload at depth d."""
-    codes = np.ascontiguousarray(codes)
-    return codes.astype(np.uint8) if d == 8 else np.ascontiguousarray(codes.astype("<u2")).view(np.uint8)
-
-
-def from_payload(payload, d):
-    payload = np.ascontiguousarray(np.asarray(payload))
-    return payload.astype(np.int64) if d == 8 else payload.view("<u2").astype(np.int64)
-
 
 def _rand_payload(rng, n, h, w, d, top=None):
     return to_payload(rng.integers(0, top or 2 ** d, size=(n, samples_of(h, w))), d)
-
-
-def assert_codes_close(got, want, frac):
-    """Every sample within 1 code; at most `frac` of them differ at all."""
-    diff = np.abs(np.asarray(got).astype(np.int64) - np.asarray(want).astype(np.int64))
-    print("codes: max difference %d, %d of %d differ (cap %g)" % (diff.max(), (diff > 0).sum(), diff.size, frac))
-    assert diff.max() <= 1, diff.max()
-    assert (diff > 0).sum() <= frac * diff.size, ((diff > 0).sum(), diff.size)
 
 
 @pytest.fixture(params=BACKENDS)
@@ -129,18 +33,10 @@ def dev(request):
     return select(request.param)
 
 
-def ns(**k):
-    return types.SimpleNamespace(**k)
-
-
 COLOURS = [(m, f) for m in ("bt601", "bt709") for f in (False, True)]
 
 
 # ---------------------------------------------------------------------------------------------------- 1. Y4M (host only)
-def _stream(header, payloads, frame_line=b"FRAME\n"):
-    return header + b"".join(frame_line + bytes(p) for p in payloads)
-
-
 def test_y4m_deep_streams_need_max_depth():
     rng = np.random.default_rng(0)
     h, w = 5, 7
@@ -208,7 +104,7 @@ def test_deep_decode_matches_the_numpy_contract(dev, d):
             for matrix, full in COLOURS:
                 got = ops.i420_to_image(x, h, w, siting, matrix, full, depth=d)
                 assert got.shape == (2, 3, h, w) and got.dtype == torch.float32
-                err = float(np.abs(got.cpu().double().numpy() - np_decode(from_payload(fr, d), h, w, siting, matrix, full, d)).max())
+                err = float(np.abs(got.cpu().double().numpy() - np_decode(from_payload(fr, d), h, w, "420", siting, matrix, full, d)).max())
                 worst = max(worst, err)
                 assert err < 2e-6, (d, h, w, siting, matrix, full, err)
     print("deep decode, depth %d: max abs error %.3g" % (d, worst))
@@ -220,7 +116,7 @@ def test_deep_decode_takes_out_of_range_samples_and_refuses_bad_arguments(dev):
     h, w = 5, 7
     fr = _rand_payload(rng, 2, h, w, 10, top=65536)     # stored values above 2^10 - 1: taken as they are, the clamp deals with them
     got = ops.i420_to_image(torch.from_numpy(fr).to(dev), h, w, "jpeg", "bt709", False, depth=10)
-    assert float(np.abs(got.cpu().double().numpy() - np_decode(from_payload(fr, 10), h, w, "jpeg", "bt709", False, 10)).max()) < 2e-6
+    assert float(np.abs(got.cpu().double().numpy() - np_decode(from_payload(fr, 10), h, w, "420", "jpeg", "bt709", False, 10)).max()) < 2e-6
     x = torch.from_numpy(fr).to(dev)
     with pytest.raises(ValueError):
         ops.i420_to_image(x, h, w, depth=8)              # the payload size of another depth
@@ -255,7 +151,7 @@ def test_encode_textbook_codes(dev):
         t = np.broadcast_to(np.array(signs, np.float32)[None, None, None, :], (n, h, w, 3)).copy()
         want = np.concatenate([np.full((n, plane), codes[0]), np.full((n, plane // 4), codes[1]), np.full((n, plane // 4), codes[2])], axis=1)
         for ft in (np.float32, np.float64):              # the contract itself gives the textbook numbers
-            assert np.array_equal(np_encode(t.transpose(0, 3, 1, 2), matrix, full, d, ft), want), (d, matrix, full, signs, ft)
+            assert np.array_equal(np_encode(t.transpose(0, 3, 1, 2), "420", matrix, full, d, ft), want), (d, matrix, full, signs, ft)
         out = ops.image_to_i420(torch.from_numpy(t).to(dev), matrix, full, depth=d)
         assert out.dtype == torch.uint8 and out.shape == (n, 2 * plane * 3 // 2)
         assert L.lib().fsr_last_kernel().decode() == "image_to_i420_kernel<u16>"
@@ -282,7 +178,7 @@ def test_float32_restatement_is_inside_the_caps():
         for shape in ENC_SHAPES:
             t = _enc_input(shape).numpy().transpose(0, 3, 1, 2)
             for matrix, full in COLOURS:
-                a, b = np_encode(t, matrix, full, d, np.float32), np_encode(t, matrix, full, d, np.float64)
+                a, b = np_encode(t, "420", matrix, full, d, np.float32), np_encode(t, "420", matrix, full, d, np.float64)
                 assert np.abs(a - b).max() <= 1
                 differ, total = differ + int((a != b).sum()), total + a.size
         print("float32 restatement, depth %d: %d of %d samples differ (%.4f %%)" % (d, differ, total, 100.0 * differ / total))
@@ -298,7 +194,7 @@ def test_encode_random(dev, d):
             out = ops.image_to_i420(t.to(dev), matrix, full, depth=d)
             assert out.dtype == torch.uint8 and out.shape == (n, ops.i420_frame_bytes(h, w, d))
             assert L.lib().fsr_last_kernel().decode() == ("image_to_i420_kernel<u8>" if d == 8 else "image_to_i420_kernel<u16>")
-            want = np_encode(t.numpy().transpose(0, 3, 1, 2), matrix, full, d)
+            want = np_encode(t.numpy().transpose(0, 3, 1, 2), "420", matrix, full, d)
             assert_codes_close(from_payload(out.cpu().numpy(), d), want, CAP[d])
 
 
@@ -315,14 +211,6 @@ def test_encode_is_the_resamplers_i420_stage_at_the_native_size(dev, shape):
             assert a.shape == b.shape and torch.equal(a, b), (d, matrix, full)
 
 
-def _aa_matrix(n_in, n_out):
-    xmin, xsize, taps, _ = dataloader.aa_bicubic_taps(n_in, n_out)
-    m = np.zeros((n_out, n_in))
-    for i in range(n_out):
-        m[i, xmin[i]:xmin[i] + xsize[i]] = taps[i, :xsize[i]].astype(np.float64)
-    return m
-
-
 def test_deep_resize_against_the_tap_composition(dev):
     (h, w), (oh, ow), d = (9, 14), (20, 26), 10
     t = torch.rand(2, h, w, 3, generator=torch.Generator().manual_seed(9)) * 2.2 - 1.1
@@ -332,7 +220,7 @@ def test_deep_resize_against_the_tap_composition(dev):
         got = ops.resample_image(t.to(dev), oh, ow, "i420", matrix, full, depth=d)
         assert L.lib().fsr_last_kernel().decode() == "resample_kernel<i420,5,u16>"
         assert got.dtype == torch.uint8 and got.shape == (2, ops.i420_frame_bytes(oh, ow, d))
-        assert_codes_close(from_payload(got.cpu().numpy(), d), np_encode(2.0 * np.clip(v, 0.0, 1.0) - 1.0, matrix, full, d), CAP[d])
+        assert_codes_close(from_payload(got.cpu().numpy(), d), np_encode(2.0 * np.clip(v, 0.0, 1.0) - 1.0, "420", matrix, full, d), CAP[d])
 
 
 def test_encode_refusals(dev):
@@ -362,12 +250,6 @@ def test_encode_refusals(dev):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. the whole generator
-def _tiny(pkg, dev):
-    G = pkg.Generator(ns(n_filters=16, n_layers=1), compute_dtype="f32")
-    G.load_state_dict(sd_from(load_npz("g_tiny.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 def _check_forward(G, fr, h, w, d, od, dev, colour, out_colour):
     """forward_yuv420 at (d, od) against the numpy encode of the same model's float forward() on the device-decoded frames."""
     x = torch.from_numpy(fr).to(dev)
@@ -378,7 +260,7 @@ def _check_forward(G, fr, h, w, d, od, dev, colour, out_colour):
     assert got.dtype == torch.uint8 and got.shape == (fr.shape[0], ops.i420_frame_bytes(4 * h, 4 * w, od))
     with torch.no_grad():
         t = G(ops.i420_to_image(x, h, w, "mpeg2", colour[0], colour[1], depth=d)).cpu().numpy()
-    assert_codes_close(from_payload(got.cpu().numpy(), od), np_encode(t, out_colour[0], out_colour[1], od), CAP[od])
+    assert_codes_close(from_payload(got.cpu().numpy(), od), np_encode(t, "420", out_colour[0], out_colour[1], od), CAP[od])
     return kernel
 
 
@@ -403,12 +285,6 @@ def test_forward_yuv420_depths_tiny_generator(dev, pkg):
 
 
 # ---------------------------------------------------------------------------------------------------- 6. GPU: shipped weights
-def _shipped(pkg, dev, cdn):
-    G = pkg.Generator(ns(n_filters=64, n_layers=8), compute_dtype=cdn)
-    G.load_state_dict(sd_from(load_npz("g_model_pt.npz"), "sd."))
-    return G.to(dev).eval()
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("cdn, d, od", [("f16", 10, 10), ("x3", 10, 10), ("f32", 8, 16)])
 def test_forward_yuv420_depths_shipped_weights_gpu(pkg, cdn, d, od, monkeypatch):
@@ -467,13 +343,6 @@ def cli_dir(tmp_path_factory):
     torch.save({"_orig_mod." + k: v for k, v in sd.items()}, d / "models" / "model.pt")
     (d / "configs" / "config.yaml").write_text("generator:\n  n_filters: 64\n  n_layers: 8\ntraining:\n  compute_dtype: f16\n")
     return d
-
-
-def _cli(cli_dir, data, *flags):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "video.py"), "--input", "-", "--output", "-", "--batch", "2"] + list(flags),
-                       input=data, capture_output=True, cwd=cli_dir, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    return r
 
 
 @pytest.mark.gpu

@@ -18,7 +18,7 @@
      interleaved round by round:
        (a) forward_yuv420, 8 bits in and out (the head's I420 epilogue);   (b) 10 bits in, 10 bits out;   (c) 8 bits in, 10 bits out
      -- (b) and (c) are the float head followed by the encode kernel -- then the encode kernel alone from its own events
-     (ops.PROFILE_ENCODE) over its algorithmic bytes: 12 B in + 3 B out per pixel.
+     (ops.PROFILE_YUV) over its algorithmic bytes: 12 B in + 3 B out per pixel.
 
   5. `--chroma`: 4:2:2 and 4:4:4.  360x640, batch 8, f16, every path one hipGraph, device events, interleaved round
      by round:
@@ -201,13 +201,13 @@ def deep_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
         for _ in range(5):
             ops.image_to_i420(t, depth=depth)
         torch.cuda.synchronize()
-        ops.PROFILE_ENCODE = []
+        ops.PROFILE_YUV = []
         for _ in range(50):
             ops.image_to_i420(t, depth=depth)
         torch.cuda.synchronize()
-        prof, ops.PROFILE_ENCODE = ops.PROFILE_ENCODE, None
-        ms = sorted(e0.elapsed_time(e1) for e0, e1, _ in prof)
-        nbytes = prof[0][2]
+        prof, ops.PROFILE_YUV = ops.PROFILE_YUV, None
+        ms = sorted(e0.elapsed_time(e1) for _, _, e0, e1, _ in prof)
+        nbytes = prof[0][4]
         print("deep        kernel image_to_i420_kernel<%s> %dx%d batch %d: median %.1f us, min %.1f us (own events, 50 launches); "
               "%.1f MB algorithmic -> %.2f TB/s at the median" % ("u8" if depth == 8 else "u16", 4 * h, 4 * w, b, 1e3 * ms[len(ms) // 2],
                                                                1e3 * ms[0], nbytes / 1e6, nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
@@ -265,8 +265,8 @@ def chroma_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
             fn()
         torch.cuda.synchronize()
         prof, ops.PROFILE_YUV = ops.PROFILE_YUV, None
-        ms = sorted(e0.elapsed_time(e1) for _, e0, e1, _ in prof)
-        nbytes = prof[0][3]
+        ms = sorted(e0.elapsed_time(e1) for _, _, e0, e1, _ in prof)
+        nbytes = prof[0][4]
         print("chroma      kernel %-30s %dx%d batch %d: median %.1f us, min %.1f us (own events, 50 launches); "
               "%.1f MB algorithmic -> %.2f TB/s at the median" % (name, kh, kw, b, 1e3 * ms[len(ms) // 2], 1e3 * ms[0], nbytes / 1e6,
                                                                nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
