@@ -23,6 +23,10 @@ parser.add_argument("--image_dir", default=None, required=True, type=str)
 parser.add_argument("--output_dir", default=None, required=True, type=str)
 parser.add_argument("--compute_dtype", default=None, choices=["bf16", "f16", "x3", "x3v", "f32"], help="extension: kernel precision")
 parser.add_argument("--batch", default=8, type=int, help="extension: frames per device batch (same-shape frames are batched)")
+parser.add_argument("--bands", default="auto", choices=["auto", "on", "off"],
+                    help="extension: run the generator's tail in row bands -- auto: for frames too large otherwise (above 1080p); on: whenever "
+                         "that allows a larger batch; off: never")
+parser.add_argument("--band_rows", default=128, type=int, help="extension: core rows per band")
 _size_flags = parser.add_mutually_exclusive_group()
 _size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="extension: exact output size (default: 4x the input)")
 _size_flags.add_argument("--scale", default=None, type=float, help="extension: output size relative to the INPUT, e.g. 2 or 1.5")
@@ -87,9 +91,12 @@ class InferencePipeline:
     `run_yuv420` is the same under its I420 name.
     Output size: every run method takes out_size = (out_h, out_w) (Generator.forward_u8 / forward_yuv: the fused resize
     after the head, captured in the same graph).  Plans of a resized output append ("size", out_h, out_w) to the key of the
-    native plan, so both coexist; None or the native size IS the native plan."""
+    native plan, so both coexist; None or the native size IS the native plan.
+    Row bands: bands="auto" runs the generator's tail in bands of `band_rows` core rows for the shapes that cannot run
+    otherwise (max_batch(h, w) == 0: above 1080p for the shipped model), "on" for every shape whose batch that enlarges, "off" (the
+    default) never.  The frames are the same bytes; banded plans append ("bands", band_rows) to their key."""
 
-    def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4):
+    def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4, bands="off", band_rows=128):
         """copy=False: `run` yields VIEWS of the pinned result buffers (valid until `depth` more batches have been
         submitted) instead of private arrays -- for consumers that encode / display a frame right away.
         max_shapes: plans (pinned staging, device buffers, captured graphs with their private pools) are kept for the
@@ -97,6 +104,11 @@ class InferencePipeline:
         per-image loop handles, inference.py:47-57) would otherwise pin a few GB per distinct shape for good."""
         self.model, self.device, self.batch, self.depth, self.use_graph = model.eval(), torch.device(device), batch, depth, use_graph
         self.copy = copy
+        if bands not in ("auto", "on", "off"):
+            raise ValueError("bands must be 'auto', 'on' or 'off', got %r" % (bands,))
+        if isinstance(band_rows, bool) or int(band_rows) != band_rows or band_rows < 1:
+            raise ValueError("band_rows must be a positive integer, got %r" % (band_rows,))
+        self.bands, self.band_rows = bands, int(band_rows)
         self.max_shapes = max(1, int(max_shapes))
         self._plans = {}            # (h, w) -> list of `depth` slots, built lazily (a one-batch bucket only ever builds slot 0)
         self._lru = []              # shapes, least recently used first
@@ -108,6 +120,19 @@ class InferencePipeline:
         below 2^31 elements, and InstanceNorm statistics are per image, so a smaller batch computes the same frames.  A frame
         that is too large on its own is refused here, before anything is allocated."""
         limit = self.model.max_batch(h, w) if hasattr(self.model, "max_batch") else self.batch
+        if self._bands_for(h, w, limit) is not None:
+            limit = self.model.max_batch(h, w, bands=True)
+            if limit < 1:
+                px = self.model.max_batch(1, 1, bands=True)
+                raise ValueError("frames of %dx%d are too large: even with the tail in row bands a frame's largest activation would hold "
+                                 "2^31 or more elements, the limit of the convolution kernels (max_batch = 0; the limit is %d input "
+                                 "pixels per frame, %.1f M)" % (w, h, px, px / 1e6))
+            b = min(self.batch, limit)
+            if (h, w) not in self._told:
+                self._told.add((h, w))
+                print("InferencePipeline: %dx%d frames run banded (the generator's tail in bands of %d rows), in batches of %d"
+                      % (w, h, self.band_rows, b), file=sys.stderr)
+            return b
         if limit < 1:
             raise ValueError("frames of %dx%d are too large: one frame's largest activation would hold 2^31 or more elements, the limit "
                              "of the convolution kernels (max_batch = 0; 1920x1080 is the largest 16:9 input)" % (w, h))
@@ -117,6 +142,15 @@ class InferencePipeline:
             print("InferencePipeline: %dx%d frames run in batches of %d instead of %d (the kernels index tensors below 2^31 elements)"
                   % (w, h, b, self.batch), file=sys.stderr)
         return b
+
+    def _bands_for(self, h, w, whole=None):
+        """Core rows per band for h x w inputs, or None when the shape runs whole: "auto" bands a shape that cannot run otherwise,
+        "on" every shape whose whole-frame limit is below the batch asked for."""
+        if self.bands == "off" or not hasattr(self.model, "max_batch") or not len(self.model.upsampling):
+            return None
+        if whole is None:
+            whole = self.model.max_batch(h, w)
+        return self.band_rows if whole < (1 if self.bands == "auto" else self.batch) else None
 
     class _Slot:
         pass
@@ -244,7 +278,7 @@ class InferencePipeline:
         out_size = (out_h, out_w): payloads of that size.  depth / out_depth (8..16, out_depth defaults to depth): bits per sample in and
         out; payloads deeper than 8 bits are 2 bytes per sample and still travel as uint8 arrays.
         Plan keys: ("i420", h, w, colour parameters), then ("size", out_h, out_w) for a resized output, ("depth", depth, out_depth) for any
-        pair but (8, 8) and ("chroma", chroma, out_chroma) for any pair but ("420", "420")."""
+        pair but (8, 8), ("chroma", chroma, out_chroma) for any pair but ("420", "420") and ("bands", band_rows) for a banded plan."""
         out_chroma = chroma if out_chroma is None else out_chroma
         if siting is None:
             siting = "mpeg2" if chroma == "422" else "jpeg"
@@ -259,10 +293,13 @@ class InferencePipeline:
             key += ("depth", depth, out_depth)
         if (chroma, out_chroma) != ("420", "420"):
             key += ("chroma", chroma, out_chroma)
+        batch, rows = self._batch_for(h, w), self._bands_for(h, w)
+        if rows is not None:
+            key += ("bands", rows)
         fmt = self._Format(key, (yuv_frame_bytes(h, w, chroma, depth),),
                            lambda x: model.forward_yuv(x, h, w, chroma=chroma, out_chroma=out_chroma, out_size=out_size, depth=depth,
-                                                       out_depth=out_depth, **colour),
-                           self._batch_for(h, w))
+                                                       out_depth=out_depth, bands=rows, **colour),
+                           batch)
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)
 
@@ -281,11 +318,15 @@ class InferencePipeline:
                 return
             h, w = first.shape[0], first.shape[1]
             size = self._out_size(h, w, out_size)
-            if size is None:
-                fmt = self._Format((h, w), (h, w, 3), self.model.forward_u8, self._batch_for(h, w))
+            batch, rows = self._batch_for(h, w), self._bands_for(h, w)
+            key = (h, w) if size is None else (h, w, "size") + size
+            if rows is not None:
+                fmt = self._Format(key + ("bands", rows), (h, w, 3),
+                                   lambda x, m=self.model, sz=size, r=rows: m.forward_u8(x, out_size=sz, bands=r), batch)
+            elif size is None:
+                fmt = self._Format(key, (h, w, 3), self.model.forward_u8, batch)
             else:
-                fmt = self._Format((h, w, "size") + size, (h, w, 3), lambda x, m=self.model, sz=size: m.forward_u8(x, out_size=sz),
-                                   self._batch_for(h, w))
+                fmt = self._Format(key, (h, w, 3), lambda x, m=self.model, sz=size: m.forward_u8(x, out_size=sz), batch)
         batch = fmt.batch
         while True:
             chunk = [] if first is None else [first]
@@ -343,7 +384,8 @@ def main(argv=None):
     image_paths = sorted(x for x in os.listdir(args.image_dir)
                          if x.lower().endswith(".png") or x.lower().endswith(".jpg") or x.lower().endswith("jpeg"))
     print(f"Found {len(image_paths)} to super resolve, starting...")
-    pipe = InferencePipeline(model, device, batch=args.batch)      # (reports a batch it has to reduce for large frames, once per size)
+    # (reports a batch it has to reduce for large frames, and a size it runs in row bands, once per size)
+    pipe = InferencePipeline(model, device, batch=args.batch, bands=args.bands, band_rows=args.band_rows)
     resolve_out_size(1, 1, args.size, args.scale)      # a malformed --size fails before any image is read
 
     def load(name):

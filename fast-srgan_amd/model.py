@@ -93,26 +93,35 @@ class Generator(torch.nn.Module):
             raise ValueError("out_size must be (out_h, out_w) of positive integers, got %r" % (out_size,))
         return (int(oh), int(ow)) == (s * h, s * w)
 
-    def forward_u8(self, frames, out_size=None):
+    def forward_u8(self, frames, out_size=None, bands=None):
         """Inference on raw frames (inference.py:47-57 without the host round trips): (N,H,W,3) uint8 in, (N,4H,4W,3) uint8
         out.  The [-1,1] mapping (:48) is one small kernel in front of the neck; the head's epilogue applies :53-56
         ((y+1)/2 * 255, truncating cast) and stores bytes -- a 720p frame leaves the device as 2.8 MB instead of 11 MB of
         floats.
         out_size = (out_h, out_w): frames of that size instead -- the float head output goes through one fused kernel, the
         antialiased bicubic resize with the same truncating cast (ops.resample_image).  None or the native size:
-        the head's own epilogue, as before."""
+        the head's own epilogue, as before.
+        bands = R: the tail runs in row bands of R core rows (`_tail_banded`): the same bytes, and batches up to
+        max_batch(h, w, bands=True)."""
         with torch.no_grad():
             if self._native_size(frames.shape[1], frames.shape[2], out_size):
-                return self._forward(ops.u8_to_image(frames), self._cfg_head_u8)
-            t = self._forward(ops.u8_to_image(frames), self._cfg_head)
+                return self._forward(ops.u8_to_image(frames), self._cfg_head_u8, bands)
+            t = self._forward(ops.u8_to_image(frames), self._cfg_head, bands)
             return ops.resample_image(t.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "u8")
 
-    def max_batch(self, h, w):
+    def max_batch(self, h, w, bands=False):
         """Largest batch of h x w frames the convolution kernels can index: every launcher refuses tensors of 2^31 or more elements,
         and the largest activation of a batch holds n * h * w * n_filters * 4 ** n_upsample of them (the output of the last
-        up-sampling convolution, before its pixel shuffle; with no up-sampling block, the neck's output).  0: a single frame is too large."""
-        nf = self.neck[0].out_channels
-        return (2 ** 31 - 1) // (int(h) * int(w) * nf * 4 ** len(self.upsampling))
+        up-sampling convolution, before its pixel shuffle; with no up-sampling block, the neck's output).  0: a single frame is too large.
+        bands=True: the limit of a forward with `bands` set.  That tensor then only ever exists one group of row
+        bands at a time, and the largest whole-frame tensors are the input of the last up-sampling convolution
+        (n * h * w * n_filters * 4 ** (n_upsample - 1)) and the float head output (n * h * w * 3 * 4 ** n_upsample).  With no
+        up-sampling block there is no tail to band and the limit is the same."""
+        nf, u = self.neck[0].out_channels, len(self.upsampling)
+        per = nf * 4 ** u
+        if bands and u >= 1:
+            per = max(nf * 4 ** (u - 1), 3 * 4 ** u)
+        return (2 ** 31 - 1) // (int(h) * int(w) * per)
 
     def _head_i420(self, matrix, full_range):
         """ConvCfg of the head whose epilogue stores 8-bit I420 planes in (matrix, full_range), made on first use."""
@@ -123,7 +132,7 @@ class Generator(torch.nn.Module):
         return cfg
 
     def forward_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
-                    out_full_range=None, out_size=None, depth=8, out_depth=None):
+                    out_full_range=None, out_size=None, depth=8, out_depth=None, bands=None):
         """Video inference on planar YUV frames: (N, bytes) uint8 payloads of h x w (odd sizes legal) in, (N, bytes) uint8 payloads of
         (s h) x (s w) out, s = 2 ** n_upsample.  `chroma` in, `out_chroma` out ("420", "422" or "444", independent of each other;
         out_chroma defaults to chroma): payloads are ops.yuv_frame_bytes(h, w, chroma, depth) bytes in and
@@ -137,7 +146,8 @@ class Generator(torch.nn.Module):
         out_size = (out_h, out_w): payloads of that size instead (both even for "420", an even width for "422", any extents for "444").
         Routes: 8-bit "420" output at the native size (out_size None or that size) is the head's own I420 epilogue.  Anything else is the
         float head followed by ops.image_to_yuv at the native size, or by one fused kernel that resizes (antialiased bicubic) and encodes
-        (ops.resample_image) -- "444" on a 4:2:0 source keeps the chroma the head has computed."""
+        (ops.resample_image) -- "444" on a 4:2:0 source keeps the chroma the head has computed.
+        bands = R: the tail in row bands of R core rows, as forward_u8's; the encode / resize kernels run on the whole frame after it."""
         ops.chroma_code(chroma)
         out_chroma = chroma if out_chroma is None else out_chroma
         ops.chroma_code(out_chroma)
@@ -149,7 +159,7 @@ class Generator(torch.nn.Module):
         epilogue = out_chroma == "420" and native and out_depth == 8
         cfg = self._head_i420(out_matrix, out_full) if epilogue else self._cfg_head
         with torch.no_grad():
-            y = self._forward(ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth), cfg)
+            y = self._forward(ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth), cfg, bands)
             if epilogue:
                 return y
             t = y.permute(0, 2, 3, 1)
@@ -158,14 +168,71 @@ class Generator(torch.nn.Module):
             return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth, out_chroma)
 
     def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
-                       out_size=None, depth=8, out_depth=None):
+                       out_size=None, depth=8, out_depth=None, bands=None):
         """forward_yuv for I420 payloads in and out."""
-        return self.forward_yuv(frames, h, w, "420", "420", siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth)
+        return self.forward_yuv(frames, h, w, "420", "420", siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth,
+                                bands)
 
-    def forward(self, x):
-        return self._forward(x, self._cfg_head)
+    def forward(self, x, bands=None):
+        """bands = R (inference only: raises while gradients are enabled): the tail in row bands of R core rows."""
+        return self._forward(x, self._cfg_head, bands)
 
-    def _forward(self, x, cfg_head):
+    def _forward(self, x, cfg_head, bands=None):
+        m = self._body(x)
+        if bands is None or not len(self.upsampling):      # (no up-sampling block: there is no tail to band)
+            return self._tail(m, cfg_head)
+        return self._tail_banded(m, cfg_head, bands)
+
+    def _tail(self, m, cfg_head):
+        """The last up-sampling block and the head on m = `_body`'s output: local 3x3 arithmetic, no statistic."""
+        for up in list(self.upsampling)[-1:]:
+            m, _ = ops.conv3x3(m, up.conv.weight, up.conv.bias, up.relu.weight, self._cfg_up)
+        out, _ = ops.conv3x3(m, self.head[0].weight, self.head[0].bias, None, cfg_head)                # :117
+        return out
+
+    def _tail_banded(self, m, cfg_head, bands):
+        """`_tail` in row bands: the windows of ops.tail_windows over the rows of m, of all images, gathered into
+        groups of G windows, each group run through `_tail` as a batch of its own, and the core rows of every result copied to
+        their place in the whole output.  The output of the last up-sampling convolution -- the largest tensor of a forward --
+        exists one group at a time; G is the largest group the convolution kernels index."""
+        R = int(bands)
+        if isinstance(bands, bool) or R != bands or R < 1:
+            raise ValueError("bands must be None or the number of core rows per band (an integer >= 1), got %r" % (bands,))
+        if torch.is_grad_enabled():
+            raise L.FsrError("bands: the banded tail is inference-only (it has no gradient); call it under torch.no_grad()")
+        n, H2, W2, c = m.shape
+        wins = ops.tail_windows(H2, R)
+        if len(wins) == 1:
+            return self._tail(m, cfg_head)
+        Hw, total = R + 2 * ops.TAIL_HALO, n * len(wins)
+        cup = self.upsampling[-1].conv.out_channels
+        G = min(total, 65535, (2 ** 31 - 1) // (Hw * W2 * max(cup, 12)))
+        if G < 1:
+            raise ValueError("bands=%d: one window of %d x %d is too large for the convolution kernels; use fewer rows" % (R, Hw, W2))
+        es, oh, ow = m.element_size(), 2 * H2, 2 * W2
+        if cfg_head.i420_head:      # (N, bytes) uint8: the Y plane, then Cb and Cr at a quarter of its size each
+            out = torch.empty((n, oh * ow * 3 // 2), dtype=torch.uint8, device=m.device)
+            # (row bytes, output rows per row of m, plane offset in a window's payload, plane offset in a frame's)
+            planes = [(ow, 2, 0, 0), (W2, 1, 4 * Hw * W2, oh * ow), (W2, 1, 5 * Hw * W2, oh * ow + H2 * W2)]
+            src_pitch, dst_pitch = 6 * Hw * W2, oh * ow * 3 // 2
+        else:                       # (N, 4H, 4W, 3) uint8 or float32
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8 if cfg_head.u8_head else torch.float32, device=m.device)
+            row = ow * 3 * out.element_size()
+            planes = [(row, 2, 0, 0)]
+            src_pitch, dst_pitch = 2 * Hw * row, oh * row
+        group = ops._empty((G, Hw, W2, c), m.dtype, m.device)
+        for first in range(0, total, G):
+            g = min(G, total - first)
+            win = group[:g]
+            ops.copy_rows(m, win, H2 * W2 * c * es, Hw * W2 * c * es, W2 * c * es, first, g, H2, R)
+            y = self._tail(win, cfg_head)
+            y = y if (cfg_head.i420_head or cfg_head.u8_head) else y.permute(0, 2, 3, 1)      # the float head's NHWC buffer
+            for row, mul, src_off, dst_off in planes:
+                ops.copy_rows(y, out, src_pitch, dst_pitch, row, first, g, H2, R, mul, True, src_off, dst_off)
+        return out if (cfg_head.i420_head or cfg_head.u8_head) else out.permute(0, 3, 1, 2)
+
+    def _body(self, x):
+        """Everything in front of the last up-sampling block: the whole-frame part (InstanceNorm statistics are per image)."""
         cd = self.compute
         r, _ = ops.conv3x3(x, self.neck[0].weight, self.neck[0].bias, self.neck[1].weight, self._cfg_neck)  # :113
         y = r
@@ -184,10 +251,9 @@ class Generator(torch.nn.Module):
             y = ops.instnorm_act(u, st, skip[0], None, cd)
         u, st = ops.conv3x3(y, self.bottleneck[0].weight, None, None, self._cfg_in)                      # :115
         y = ops.instnorm_act(u, st, r, None, cd)
-        for up in self.upsampling:                                                                      # :116
+        for up in list(self.upsampling)[:-1]:                                                              # :116
             y, _ = ops.conv3x3(y, up.conv.weight, up.conv.bias, up.relu.weight, self._cfg_up)
-        out, _ = ops.conv3x3(y, self.head[0].weight, self.head[0].bias, None, cfg_head)                # :117
-        return out
+        return y
 
 
 class GraphedGenerator:

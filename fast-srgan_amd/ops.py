@@ -1116,6 +1116,48 @@ def u8_to_image(frames):
     return img.permute(0, 3, 1, 2)
 
 
+# ---------------------------------------------------------------------------------- row bands of the generator's tail
+TAIL_HALO = 2        # rows of the last up-sampling convolution's input discarded at each window edge that is not the frame's
+
+
+def tail_windows(H2, R):
+    """Windows of `R + 4` rows that cover a frame of H2 rows: [(start, core_lo, core_hi)].  Window k owns the core rows
+    [k R, min((k + 1) R, H2)) and starts at clamp(k R - 2, 0, H2 - (R + 4)), so a window edge either is the frame's edge or lies
+    2 rows outside the core.  H2 <= R + 4: the one window (0, 0, H2), the whole frame."""
+    H2, R = int(H2), int(R)
+    if H2 < 1 or R < 1:
+        raise ValueError("tail_windows: H2 and R must be positive, got %d and %d" % (H2, R))
+    Hw = R + 2 * TAIL_HALO
+    if H2 <= Hw:
+        return [(0, 0, H2)]
+    return [(max(0, min(lo - TAIL_HALO, H2 - Hw)), lo, min(lo + R, H2)) for lo in range(0, H2, R)]
+
+
+def copy_rows(src, dst, src_pitch, dst_pitch, row_bytes, first, count, H2, R, mul=1, scatter=False, src_offset=0, dst_offset=0):
+    """fsr_copy_rows on two contiguous tensors, taken as bytes: gathers the windows first .. first + count - 1 of tail_windows(H2, R)
+    (numbered image * windows + k over all images) from the frames in `src` into the group images of `dst`, or (scatter) copies the
+    `mul` rows per core row of each window in `src` to their place in the frames of `dst`.  Pitches: bytes between consecutive images;
+    offsets: bytes added to the bases (the planes of a planar payload).  Both extents are checked here -- the kernel cannot."""
+    _check_dev(src, dst)
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("copy_rows expects contiguous tensors")
+    H2, R, mul, first, count = int(H2), int(R), int(mul), int(first), int(count)
+    Hw = R + 2 * TAIL_HALO
+    if R >= 1 and H2 >= Hw and mul >= 1 and first >= 0 and count >= 1 and row_bytes >= 1:
+        nwin = (H2 + R - 1) // R
+        last_img = (first + count - 1) // nwin
+        frame_end = last_img * (dst_pitch if scatter else src_pitch) + H2 * mul * row_bytes
+        group_end = (count - 1) * (src_pitch if scatter else dst_pitch) + Hw * mul * row_bytes
+        src_end, dst_end = (group_end, frame_end) if scatter else (frame_end, group_end)
+        if (src_offset < 0 or dst_offset < 0 or src_offset + src_end > src.numel() * src.element_size()
+                or dst_offset + dst_end > dst.numel() * dst.element_size()):
+            raise ValueError("copy_rows: the windows %d..%d reach beyond a tensor (%d / %d bytes needed, %d / %d given)"
+                             % (first, first + count - 1, src_offset + src_end, dst_offset + dst_end,
+                                src.numel() * src.element_size(), dst.numel() * dst.element_size()))
+    L.check(L.lib().fsr_copy_rows(src.data_ptr() + src_offset, int(src_pitch), dst.data_ptr() + dst_offset, int(dst_pitch), int(row_bytes),
+                                  first, count, H2, Hw, R, mul, int(bool(scatter)), _stream()), "fsr_copy_rows")
+
+
 def check_depth(depth, lo=8):
     """The sample depth as an int, refused outside lo..16."""
     if isinstance(depth, bool) or int(depth) != depth or not lo <= depth <= 16:

@@ -22,6 +22,10 @@ keeps the chroma samples the network has computed, which a 4:2:0 output averages
 4:2:0, in the width for 4:2:2, and may be anything for 4:4:4 (an odd `--size` needs `--out_chroma` spelled out: it is checked before the
 stream is opened).  A `C422` stream is co-sited horizontally ("mpeg2"); `--siting jpeg` overrides that too.
 
+Frames above 1080p (2560x1440, up to 3840x2160) run with the generator's tail in row bands (`--bands auto`, the default):
+the same bytes a whole frame would give, `--band_rows` rows of the last up-sampling stage at a time.  `--bands on` bands smaller frames
+too, for a larger batch; `--bands off` refuses what does not fit whole.
+
 Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
 stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
 device batch at a time: a stream of any length passes through a pipe.
@@ -203,6 +207,10 @@ parser.add_argument("--out_chroma", default=None, choices=CHROMAS, help="chroma 
 parser.add_argument("--siting", default=None, choices=SITINGS,
                     help="chroma siting of the input, overriding the stream's tag (C420pN streams cannot declare one: jpeg is assumed; "
                          "C422 streams are mpeg2)")
+parser.add_argument("--bands", default="auto", choices=["auto", "on", "off"],
+                    help="run the generator's tail in row bands -- auto: for frames too large otherwise (above 1080p); on: whenever that "
+                         "allows a larger batch; off: never.  The output is the same bytes")
+parser.add_argument("--band_rows", default=128, type=int, help="core rows per band")
 _size_flags = parser.add_mutually_exclusive_group()
 _size_flags.add_argument("--size", default=None, type=str, metavar="WxH",
                          help="exact output size (default: 4x the input): both even for 4:2:0, an even width for --out_chroma 422, anything for "
@@ -262,14 +270,17 @@ def main(argv=None):
             w, h, ow, oh, "" if out_size is None else " (network %dx%d, resized)" % (s * w, s * h),
             args.matrix, "full" if full else "limited", reader.depth, out_matrix, "full" if out_full else "limited", out_depth, siting,
             ", 4:%s:%s -> 4:%s:%s" % (chroma[1], chroma[2], out_chroma[1], out_chroma[2])))
-        pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False)
+        try:
+            pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False, bands=args.bands, band_rows=args.band_rows)
+        except ValueError as exc:
+            raise SystemExit("video: %s" % exc)
         try:
             frames_out = pipe.run_yuv(reader.frames(), h, w, chroma=chroma, out_chroma=out_chroma, siting=siting, matrix=args.matrix,
                                       full_range=full, out_matrix=out_matrix, out_full_range=out_full, out_size=out_size,
                                       depth=reader.depth, out_depth=out_depth)
         except ValueError as exc:       # a frame too large for the kernels: refused before anything is allocated or written
             raise SystemExit("video: %s" % exc)
-        batch = min(args.batch, model.max_batch(h, w))      # (the pipeline has reported a batch it had to reduce)
+        batch = pipe._batch_for(h, w)       # (the pipeline has reported a batch it had to reduce, or a shape it runs in row bands)
         writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth, chroma=out_chroma)
         n, t0, t1 = 0, time.perf_counter(), None
         for y in frames_out:

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 14
+#define FSR_ABI_VERSION 15
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
@@ -413,6 +413,21 @@ int fsr_loss_scale_update(float* scale_state, float growth_interval, float growt
 int fsr_crop_resize(const uint8_t* const* images, const int* img_h, const int* img_w, const int* crop_y,
                     const int* crop_x, int n, int hr_size, int scale, const float* wtab, const int* xmin,
                     const int* xsize, int kmax, float* hr_out, float* lr_out, float* tmp, fsr_stream_t stream);
+
+/* ------------------------------------------------------------------ strided row-block copy (ABI 15; the banded tail)
+ * A frame of H2 rows is covered by nwin = ceil(H2 / R) windows of Hw >= R + 4 rows: window k owns the core rows
+ * [k R, min((k + 1) R, H2)) and starts at row s_k = clamp(k R - 2, 0, H2 - Hw).  The windows of all images are numbered
+ * f = image * nwin + k; one call moves the windows f = first .. first + count - 1 (count <= 65535), window f being image f - first
+ * of the group buffer:
+ *   scatter = 0 (gather): rows [s_k, s_k + Hw) of image f / nwin of `src` -> rows [0, Hw) of group image f - first of `dst`;
+ *   scatter = 1: rows [(k R - s_k) mul, (core_hi - s_k) mul) of group image f - first of `src` -> rows [k R mul, core_hi mul) of
+ *                image f / nwin of `dst` (mul: rows of this tensor per row the windows are counted in).
+ * Rows are row_bytes bytes, back to back inside an image; consecutive images lie src_pitch / dst_pitch bytes apart (a plane of a
+ * planar payload: bases at the plane, pitches of the payload).  All offsets are 64-bit.  16-byte accesses when both bases, both
+ * pitches and row_bytes are multiples of 16, else 4-byte, else single bytes (fsr_last_kernel() names the width).  The caller
+ * vouches for the extents of both buffers; null pointers, non-positive extents, R < 1, Hw > H2 and Hw < R + 4 are refused. */
+int fsr_copy_rows(const void* src, long long src_pitch, void* dst, long long dst_pitch, long long row_bytes, int first, int count,
+                  int H2, int Hw, int R, int mul, int scatter, fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ PNG -> .npy ingest (host code, no device work)
  * train.py:22-37 of the reference converts the data set once: PIL decode -> RGB -> uint8 CHW -> np.save, on 16 Python threads.

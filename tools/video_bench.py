@@ -27,10 +27,19 @@
      events (ops.PROFILE_YUV) over their algorithmic bytes: decode 12 B out + 3 (4:4:4) or 2 (4:2:2) B in per pixel at 8 bits, encode
      12 B in + 3 or 2 B out.
 
+  6. `--bands`: the generator's tail in row bands.  forward_u8, every path one hipGraph, device events, interleaved
+     round by round, f16 and x3 (`--modes`):
+       (a) 1080p, batch 1: whole against banded at R = 32 / 64 / 128 -- the cost of banding where both paths exist;
+       (b) 720p: batch 2 whole against batch 8 banded at R = 128 (the default band_rows), frames per second;
+       (c) 1440p (batch 2) and 2160p (batch 1) banded at R = 128: sizes the whole path refuses;
+       (d) the row-copy kernel alone from its own events (f16, 1080p, R = 128): the gather of the last up-sampling convolution's
+           input and the scatter of the uint8 frame, over the bytes moved (read + written).
+
     python tools/video_bench.py [--frames 2048] [--rounds 7] [--replays 20] [--modes f16,x3]
     python tools/video_bench.py --resize [--rounds 7] [--replays 20]
     python tools/video_bench.py --deep [--rounds 7] [--replays 20]
     python tools/video_bench.py --chroma [--rounds 7] [--replays 20]
+    python tools/video_bench.py --bands [--rounds 7] [--replays 20] [--modes f16,x3]
 """
 import argparse
 import importlib
@@ -273,6 +282,118 @@ def chroma_leg(sd, rounds, replays, mode="f16", h=360, w=640, b=8, d=10):
     return med
 
 
+def _interleaved(paths, rounds, replays):
+    """Per-path lists of seconds per batch: `rounds` rounds over all the graphs, the order reversed every other round."""
+    times = [[] for _ in paths]
+    for _, g, _ in paths:
+        time_graph(g, 2)
+    for r in range(rounds):
+        order = list(range(len(paths)))
+        for i in (order if r % 2 == 0 else order[::-1]):
+            times[i].append(time_graph(paths[i][1], replays))
+    return times
+
+
+def bands_leg(sd, rounds, replays, mode, R=128):
+    dev = "cuda:0"
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+
+    def frames(b, h, w):
+        return torch.from_numpy(rng.integers(0, 256, size=(b, h, w, 3), dtype=np.uint8)).to(dev)
+
+    def report(tag, paths, times):
+        med = [statistics.median(t) for t in times]
+        for (name, _, b), m, t in zip(paths, med, times):
+            spread = 100.0 * (max(t) - min(t)) / m
+            print("bands       %-4s %-4s %-30s %9.3f ms/batch  %7.2f FPS   spread %.2f %%   [per-round ms %s]" % (
+                mode, tag, name, 1e3 * m, b / m, spread, " ".join("%.3f" % (1e3 * v) for v in t)), flush=True)
+        return med
+
+    # (a) 1080p, batch 1: whole against banded
+    x = frames(1, 1080, 1920)
+    peaks = []
+    for r in (None, R):         # eager, before any graph holds a pool: the same bytes, and the peak activation memory of either path
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        peaks.append((G.forward_u8(x, bands=r), (torch.cuda.max_memory_allocated() - base) / 1e9))
+    assert torch.equal(peaks[0][0], peaks[1][0])
+    print("bands       %-4s (a)  1080p batch 1 peak activation memory: whole %.2f GB, banded R=%d %.2f GB" % (mode, peaks[0][1], R, peaks[1][1]),
+          flush=True)
+    del peaks
+    paths = [("1080p batch 1 whole", graphed(G.forward_u8, x), 1)]
+    paths += [("1080p batch 1 banded R=%d" % r, graphed(lambda t, r=r: G.forward_u8(t, bands=r), x), 1) for r in (32, 64, 128)]
+    med = report("(a)", paths, _interleaved(paths, rounds, replays))
+    print("bands       %-4s (a)  banded - whole: %s" % (mode, ";  ".join(
+        "R=%d %+.3f ms (%+.2f %%)" % (r, 1e3 * (m - med[0]), 100.0 * (m / med[0] - 1.0)) for r, m in zip((32, 64, 128), med[1:]))), flush=True)
+    del paths, x
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    # (b) 720p: batch 2 whole against batch 8 banded
+    x2, x8 = frames(2, 720, 1280), frames(8, 720, 1280)
+    paths = [("720p batch 2 whole", graphed(G.forward_u8, x2), 2), ("720p batch 8 banded R=%d" % R, graphed(lambda t: G.forward_u8(t, bands=R), x8), 8)]
+    times = _interleaved(paths, rounds, max(2, replays // 2))
+    med = report("(b)", paths, times)
+    print("bands       %-4s (b)  FPS banded batch 8 / whole batch 2 = %.4f" % (mode, (8 / med[1]) / (2 / med[0])), flush=True)
+    del paths, x2, x8
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    # (c) sizes the whole path refuses
+    for b, h, w in ((2, 1440, 2560), (1, 2160, 3840)):
+        x = frames(b, h, w)
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        paths = [("%dx%d batch %d banded R=%d" % (w, h, b, R), graphed(lambda t: G.forward_u8(t, bands=R), x), b)]
+        report("(c)", paths, _interleaved(paths, min(rounds, 3), max(2, replays // 4)))
+        print("bands       %-4s (c)  %dx%d batch %d peak activation memory %.2f GB" % (mode, w, h, b, (torch.cuda.max_memory_allocated() - base) / 1e9),
+              flush=True)
+        del paths, x
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+
+
+def rows_kernel_leg(sd, mode="f16", h=1080, w=1920, R=128):
+    """(d): fsr_copy_rows alone, from its own events: one launch over all the windows of a 1080p frame."""
+    dev = "cuda:0"
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+    x = torch.from_numpy(rng.integers(0, 256, size=(1, h, w, 3), dtype=np.uint8)).to(dev)
+    with torch.no_grad():
+        m = G._body(ops.u8_to_image(x))
+    _, H2, W2, c = m.shape
+    nwin, Hw, es = len(ops.tail_windows(H2, R)), R + 4, m.element_size()
+    group = torch.empty((nwin, Hw, W2, c), dtype=m.dtype, device=dev)
+    y = torch.empty((nwin, 2 * Hw, 2 * W2, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty((1, 2 * H2, 2 * W2, 3), dtype=torch.uint8, device=dev)
+    row, orow = W2 * c * es, 2 * W2 * 3
+    runs = [("gather  %dx%dx%d %s -> %d windows of %d rows" % (H2, W2, c, mode, nwin, Hw), 2 * nwin * Hw * row,
+             lambda: ops.copy_rows(m, group, H2 * row, Hw * row, row, 0, nwin, H2, R)),
+            ("scatter uint8 frame %dx%d" % (2 * H2, 2 * W2), 2 * 2 * H2 * orow,
+             lambda: ops.copy_rows(y, out, 2 * Hw * orow, 2 * H2 * orow, orow, 0, nwin, H2, R, 2, True))]
+    for name, nbytes, fn in runs:
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        evs = []
+        for _ in range(50):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            evs.append((e0, e1))
+        torch.cuda.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+        print("bands       (d)  kernel %s  %-52s median %.1f us, min %.1f us (own events, 50 launches); %.1f MB read + written -> "
+              "%.2f TB/s at the median" % (ops._last_kernel(), name, 1e3 * ms[len(ms) // 2], 1e3 * ms[0], nbytes / 1e6,
+                                           nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
+
+
 def end_to_end(sd, frames, mode):
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "configs"))
@@ -312,6 +433,7 @@ def main():
     ap.add_argument("--resize", action="store_true", help="run the arbitrary-output-size leg only")
     ap.add_argument("--deep", action="store_true", help="run the deep-sample leg only")
     ap.add_argument("--chroma", action="store_true", help="run the 4:2:2 / 4:4:4 leg only")
+    ap.add_argument("--bands", action="store_true", help="run the row-band leg only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("video_bench needs the MI355X")
@@ -325,6 +447,11 @@ def main():
         return
     if args.chroma:
         chroma_leg(sd, args.rounds, args.replays)
+        return
+    if args.bands:
+        for mode in args.modes.split(","):
+            bands_leg(sd, args.rounds, args.replays, mode)
+        rows_kernel_leg(sd)
         return
     model = {}
     for mode in args.modes.split(","):
