@@ -34,7 +34,7 @@ struct C3Args {
   int cout;             // multiple of 16
   void* out;            // forward: [N,H,W,cout] T
   void* preact;
-  unsigned char* signs; // forward, optional: [N,H,W,cout/8] -- bit (c & 7) of byte c >> 3 = (out[c] > 0), read by conv_s2d3.hip as the activation-gradient mask
+  unsigned char* signs; // forward, optional: [N,H,W,cout/8] -- bit (c & 7) of byte c >> 3 = (out[c] > 0; x3: its hi part), read by conv_s2d3.hip as the activation-gradient mask
   const void* dz;       // wgrad: [N,H,W,cout] T
   float* ws;            // wgrad partials [slab][cout][32]
   int tiles_x, tiles_y, tiles_per_slab, ntiles;
@@ -55,7 +55,8 @@ template <> __device__ __forceinline__ float round_T<f16_t>(float v) { return (f
 
 // Ablation builds (tools/build_variant.sh <suffix> -DFSR_ABLC3=<mask>; results WRONG on purpose, the product library is built
 // with 0):  1 no output stores (forward) / no dz loads (weight gradient)   2 no MFMAs   4 no LDS traffic of the dz tile
-// (weight gradient; implies 2): 6 leaves the weight gradient's global loads alone
+// (weight gradient; implies 2): 6 leaves the weight gradient's global loads alone   8 no patch fetch (forward: the patch is made
+// of thread indices)   16 no filter-fragment fetch (forward: fragments made of lane indices)
 #ifndef FSR_ABLC3
 #define FSR_ABLC3 0
 #endif
@@ -136,7 +137,8 @@ __device__ __forceinline__ void stage_patch(const C3Args& a, float* patch, int n
     const int y = y0 - 1 + py, x = x0 - 1 + px;
     const bool ok = i < PN && y >= 0 && y < a.H && x >= 0 && x < a.W;
     okmask |= (ok ? 1u : 0u) << j;
-    v[j] = src[ok ? ci * a.sc + y * a.sh + x * a.sw : 0];
+    if constexpr ((C3_ABL & 8) != 0) v[j] = (float)(i & 15);
+    else v[j] = src[ok ? ci * a.sc + y * a.sh + x * a.sw : 0];
   }
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
@@ -151,10 +153,22 @@ __device__ __forceinline__ void stage_patch(const C3Args& a, float* patch, int n
 // ------------------------------------------------------------------ forward
 // ST = storage type of the 64-channel tensors.  FSR_X3 runs the exact-f32 arithmetic (T = float: the layer is bound by writing
 // its output, and K = 27 f32 MFMA steps cost less than that) on x3 storage (ST = x3_t): better than the three-MFMA form, for free.
-template <typename T, typename ST = T>
+//
+// A workgroup covers a strip of ROWS rows x 16 columns x 64 output channels; wave w owns rows [w ROWS/4, (w+1) ROWS/4).
+// ROWS = 16 is the one-tile kernel: patch staged, then filter fragments, barrier, bias, rows.  About 0.7 (x3) / 0.6 (f16) of
+// that kernel is this preamble, paid per 16 rows (profiles/c3_stream_ablation.txt, section 3).  The taller strips (32, 64) pay it
+// once per strip and order it differently: EVERY global load of the workgroup -- the patch (up to 14 values per thread), the
+// filter fragments, bias, slope -- is issued before the first use of any of them, then the patch is normalised into LDS, one
+// barrier, and the row loop makes no global load: nothing of a later row can queue behind an earlier row's stores (loads and
+// stores share one counter; what sank the persistent walk, docs/HISTORY.md).  A row at or beyond H (ragged last strip) is
+// skipped wave-uniformly.  Arithmetic, channel deal, store shapes and sign bytes do not depend on ROWS.
+template <typename T, typename ST = T, int ROWS = 16>
 __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
-  constexpr int TH = 16;
-  __shared__ float patch[(TH + 2) * PW * 3];
+  constexpr int TH = ROWS, RPW = ROWS / 4;        // rows per wave
+  constexpr int PN = (TH + 2) * PW * 3, PPT = (PN + 255) / 256;
+  constexpr bool STRIP = ROWS > 16;
+  static_assert(ROWS == 16 || ROWS == 32 || ROWS == 64, "strip height");
+  __shared__ float patch[PN];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lg = lane >> 4;
   int bid = blockIdx.x;
@@ -164,7 +178,26 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
   const int n = bid / a.tiles_y;
   const int nb = blockIdx.y;                      // block of 64 output channels
   const int ntile = (a.cout - nb * 64 >= 64) ? 4 : (a.cout - nb * 64) / 16;
-  stage_patch<T, TH>(a, patch, n, ty * TH, tx * 16, tid);
+  float pv[PPT];                                  // strips: the thread's patch values between their loads and the LDS image
+  unsigned okmask = 0u;
+  if constexpr (!STRIP) {
+    stage_patch<T, TH>(a, patch, n, ty * TH, tx * 16, tid);
+  } else {      // (addresses clamped and values discarded outside the image, as in stage_patch; the host takes strips only where
+                // an image's element offsets fit 32 unsigned bits: one address register per load in flight instead of two)
+    const float* src = a.img + n * a.sn;
+    const unsigned usc = (unsigned)a.sc, ush = (unsigned)a.sh, usw = (unsigned)a.sw;
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      const int i = tid + j * 256;
+      const int ci = i % 3, p = i / 3;
+      const int px = p % PW, py = p / PW;
+      const int y = ty * TH - 1 + py, x = tx * 16 - 1 + px;
+      const bool ok = i < PN && y >= 0 && y < a.H && x >= 0 && x < a.W;
+      okmask |= (ok ? 1u : 0u) << j;
+      if constexpr ((C3_ABL & 8) != 0) pv[j] = (float)(i & 15);
+      else pv[j] = src[ok ? (unsigned)ci * usc + (unsigned)y * ush + (unsigned)x * usw : 0u];
+    }
+  }
 
   // this lane's patch offsets and filter fragments (loop invariant)
   const T* wpk = (const T*)a.wpk;
@@ -189,7 +222,14 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
     if (t < ntile) {
       const int ch = wide ? (t >> 1) * 32 + (l15 >> 2) * 8 + (t & 1) * 4 + (l15 & 3) : t * 16 + l15;
       const T* row = wpk + (size_t)(nb * 64 + ch) * 32;
-      if constexpr (sizeof(T) == 2) {
+      if constexpr ((C3_ABL & 16) != 0) {
+        if constexpr (sizeof(T) == 2) {
+          wf16[t] = (s16x8){(short)lane, (short)t, 1, 2, 3, 4, 5, 6};
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) wf32[t][j] = (float)(lane + j);
+        }
+      } else if constexpr (sizeof(T) == 2) {
         wf16[t] = *(const s16x8*)(row + 8 * lg);
       } else {
 #pragma unroll
@@ -200,33 +240,60 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
   float slope = (a.act == FSR_ACT_PRELU) ? a.prelu[0] : a.slope;
   if (a.act == FSR_ACT_NONE) slope = 1.f;
   if (a.act == FSR_ACT_RELU) slope = 0.f;
+  // the lane's bias values, fetched BEFORE the first store (a load issued after a store waits for that store: one
+  // counter for both); wide layout: [pair][low / high run], plain: [tile].  Strips: with the other loads.
+  f32x4 bv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) bv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto load_bias = [&]() {
+    if (a.bias) {
+      if (wide) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          bv[2 * p] = *(const f32x4*)(a.bias + nb * 64 + p * 32 + lg * 8);
+          bv[2 * p + 1] = *(const f32x4*)(a.bias + nb * 64 + p * 32 + lg * 8 + 4);
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          if (t < ntile) bv[t] = *(const f32x4*)(a.bias + nb * 64 + t * 16 + lg * 4);
+      }
+    }
+  };
+  if constexpr (STRIP) {
+    load_bias();
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+      const int i = tid + j * 256;
+      const int ci = i % 3;
+      const float sc = ci == 0 ? a.scale[0] : (ci == 1 ? a.scale[1] : a.scale[2]);
+      const float sh = ci == 0 ? a.shift[0] : (ci == 1 ? a.shift[1] : a.shift[2]);
+      if (i < PN) patch[i] = ((okmask >> j) & 1u) ? round_T<T>(pv[j] * sc + sh) : 0.f;
+    }
+  }
   __syncthreads();
 
   ST* outp = (ST*)a.out;
   ST* prep = (ST*)a.preact;
   const int gx = tx * 16 + l15;
-  // the lane's bias values, fetched BEFORE the first store (a load issued after a store waits for that store: one
-  // counter for both); wide layout: [pair][low / high run], plain: [tile]
-  f32x4 bv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) bv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  if (a.bias) {
-    if (wide) {
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        bv[2 * p] = *(const f32x4*)(a.bias + nb * 64 + p * 32 + lg * 8);
-        bv[2 * p + 1] = *(const f32x4*)(a.bias + nb * 64 + p * 32 + lg * 8 + 4);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (t < ntile) bv[t] = *(const f32x4*)(a.bias + nb * 64 + t * 16 + lg * 4);
+  if constexpr (!STRIP) load_bias();
+#pragma unroll 1
+  for (int m0 = 0; m0 < RPW; m0 += 4) {
+    // strips: the loop counter as the row loop sees it is opaque, so that every store address is derived from it in place.
+    // Left to itself the compiler turns the 4 rows x (output, pre-activation) x 2 runs into sixteen 64-bit induction
+    // pointers kept across the loop: 142 registers at 64 rows, three waves per SIMD instead of four.
+    int mo = m0;
+    if constexpr (STRIP) {
+      FSR_TOUCH(mo);
+      mo = __builtin_amdgcn_readfirstlane(mo);
     }
-  }
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    const int r = wave * 4 + m;                   // row of the tile
+    const int r = wave * RPW + mo + m;            // row of the strip
     const int gy = ty * TH + r;
+    if constexpr (STRIP) {
+      if (gy >= a.H) break;                       // (uniform: the rest of this wave's rows lie below the image)
+    }
     const float* base = patch + (r * PW + l15) * 3;
     float xv[8];
 #pragma unroll
@@ -301,6 +368,16 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
             } else {
               V16<x3_t, 4>::st((x3_t*)outp + off + p * 32, v8);
             }
+            if (a.signs) {      // as in the 16-bit forms, of the STORED hi parts (what the tensor mask tests): a tiny positive value
+                                // whose hi part rounds to zero stays "not positive"
+              unsigned b = 0u;
+#pragma unroll
+              for (int q = 0; q < 4; ++q) {
+                const unsigned hh = pack_bf16x2(v8[2 * q], v8[2 * q + 1]);      // (= x3_split2's hi pair)
+                b |= ((int)(hh << 16) > 0 ? 1u << (2 * q) : 0u) | ((int)(hh & 0xffff0000u) > 0 ? 2u << (2 * q) : 0u);
+              }
+              a.signs[(((size_t)n * a.H + gy) * a.W + gx) * (a.cout >> 3) + nb * 8 + p * 4 + lg] = (unsigned char)b;
+            }
           }
         }
         continue;
@@ -347,6 +424,7 @@ __global__ __launch_bounds__(256) void conv_c3_fwd_kernel(const C3Args a) {
         }
       }
     });
+  }
   }
 }
 
@@ -584,6 +662,47 @@ int fill_args(C3Args& a, const char* what, int dtype, const float* img, long lon
   return 0;
 }
 
+// Strip height of the forward.  Strips are taken by the x3 form without a pre-activation copy, the tallest of {64, 32} rows that
+//   (a) leaves at least C3_FWD_MIN_ROUNDS rounds of workgroups over the device's 1024 slots (256 CUs x 4 resident workgroups:
+//       16 waves per CU at <= 128 registers), so that the last, partial round stays a small share of the launch, and
+//   (b) pads the map by at most H / C3_FWD_MAX_PAD rows (ceil(H / ROWS) ROWS - H: rows of patch fetched for nothing);
+// everything else gets 16 rows, the one-tile kernel.  Measured (profiles/c3_strips.txt, section 2; us per launch, 3 -> 64):
+//                                   workgroups at 64 rows     16 rows   32 rows   64 rows
+//   x3  D neck  384^2 batch 64      9216 (9.0 rounds)           811       650       603
+//   x3  G head  384^2 batch 32      4608 (4.5 rounds)           395       324       302
+//   x3  G neck   96^2 batch 32       384 (0.4 rounds)            58        64        63      -> (a): 16 rows
+//   x3  PReLU + pre-activation copy, 384^2 batch 32             541       686       725      -> 16 rows
+//   f16 D neck  384^2 batch 64                                  329       384       397      -> 16 rows
+//   f16 G head  384^2 batch 32                                  158       180       192      -> 16 rows
+// What strips amortise is the filter-fragment fetch of the f32 arithmetic, 32 dword loads per lane: without it the 16-row x3
+// kernel runs in 613 instead of 811 us, the f16 kernel (four 16-byte loads) in 341 instead of 334 (section 1 of that file).
+// The threshold of (a) sits between the 0.4 .. 0.6 rounds that lose and the 4.5 that win; plain f32 storage was not measured.
+// FSR_C3_ROWS = 16 | 32 | 64 forces a height for every form (tests, tools/ab.py; read at every call); unset or 0: this rule.
+constexpr long long C3_FWD_SLOTS = 1024;
+constexpr int C3_FWD_MIN_ROUNDS = 4, C3_FWD_MAX_PAD = 8;
+int c3_fwd_rows(int dtype, bool preact, int n, int h, int w, long long sc, long long sh, long long sw) {
+  // (the strip kernels address an image's elements with 32-bit unsigned offsets)
+  if (sc < 0 || sh < 0 || sw < 0 || 2 * sc + (long long)(h - 1) * sh + (long long)(w - 1) * sw >= (1LL << 31)) return 16;
+  if (const char* e = getenv("FSR_C3_ROWS")) {
+    const int f = atoi(e);
+    if (f == 16 || f == 32 || f == 64) return f;
+  }
+  if (dtype != FSR_X3 || preact) return 16;
+  const long long tiles_x = (w + 15) / 16;
+  for (int rows = 64; rows > 16; rows >>= 1) {
+    const long long strips = (h + rows - 1) / rows;
+    if (tiles_x * strips * n >= C3_FWD_MIN_ROUNDS * C3_FWD_SLOTS && (strips * rows - h) * C3_FWD_MAX_PAD <= h) return rows;
+  }
+  return 16;
+}
+
+template <typename T, typename ST>
+void c3_fwd_launch(int rows, dim3 grid, hipStream_t stream, const C3Args& a) {
+  if (rows == 64) hipLaunchKernelGGL((conv_c3_fwd_kernel<T, ST, 64>), grid, dim3(256), 0, stream, a);
+  else if (rows == 32) hipLaunchKernelGGL((conv_c3_fwd_kernel<T, ST, 32>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((conv_c3_fwd_kernel<T, ST, 16>), grid, dim3(256), 0, stream, a);
+}
+
 }  // namespace
 
 extern "C" int fsr_pack_conv3x3_c3(int dtype, const float* w_oihw, int cout, void* packed, int transposed, fsr_stream_t stream_) {
@@ -619,17 +738,19 @@ extern "C" int fsr_conv3x3_c3_fwd(int dtype, const float* img, long long sn, lon
   a.out = out;
   a.preact = preact;
   if (dtype == FSR_X3 && ((((size_t)out | (size_t)preact) & 127) != 0)) return fsr_fail(-2, "fsr_conv3x3_c3_fwd: x3 tensors must be 128-byte aligned");
-  if (signs && (dtype == FSR_F32 || dtype == FSR_X3 || cout % 64 != 0)) return fsr_fail(-2, "fsr_conv3x3_c3_fwd: sign bits are written by the 16-bit kernels for cout %% 64 == 0");
+  if (signs && (dtype == FSR_F32 || cout % 64 != 0)) return fsr_fail(-2, "fsr_conv3x3_c3_fwd: sign bits are written by the 16-bit and x3 kernels for cout %% 64 == 0");
   a.signs = (unsigned char*)signs;
+  const int rows = c3_fwd_rows(dtype, preact != nullptr, n, h, w, sc, sh, sw);
   a.tiles_x = (w + 15) / 16;
-  a.tiles_y = (h + 15) / 16;
+  a.tiles_y = (h + rows - 1) / rows;
   const long long nwg = (long long)a.tiles_x * a.tiles_y * n;
   if (nwg > 0x7fffffffLL) return fsr_fail(-2, "fsr_conv3x3_c3_fwd: bad grid");
   const dim3 grid((unsigned)nwg, (unsigned)((cout + 63) / 64));
-  if (dtype == FSR_BF16) hipLaunchKernelGGL(conv_c3_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream_, a);
-  else if (dtype == FSR_F16) hipLaunchKernelGGL(conv_c3_fwd_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream_, a);
-  else if (dtype == FSR_X3) hipLaunchKernelGGL((conv_c3_fwd_kernel<float, x3_t>), grid, dim3(256), 0, (hipStream_t)stream_, a);
-  else hipLaunchKernelGGL(conv_c3_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream_, a);
+  const hipStream_t stream = (hipStream_t)stream_;
+  if (dtype == FSR_BF16) c3_fwd_launch<bf16_t, bf16_t>(rows, grid, stream, a);
+  else if (dtype == FSR_F16) c3_fwd_launch<f16_t, f16_t>(rows, grid, stream, a);
+  else if (dtype == FSR_X3) c3_fwd_launch<float, x3_t>(rows, grid, stream, a);
+  else c3_fwd_launch<float, float>(rows, grid, stream, a);
   return fsr_check_launch("conv_c3_fwd_kernel");
 }
 

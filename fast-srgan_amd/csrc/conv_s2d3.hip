@@ -508,7 +508,7 @@ int s2d_launch(ConvKArgs& a, hipStream_t stream) {
 int fsr_conv_s2d3_try(int dtype, ConvKArgs& a, hipStream_t stream) {
   static const bool off = getenv("FSR_S2D3") && atoi(getenv("FSR_S2D3")) == 0;   // A/B switch
   if (off || (dtype != FSR_BF16 && dtype != FSR_F16 && dtype != FSR_X3)) return 0;
-  if (dtype == FSR_X3 && ((a.Cin & 63) != 0 || (a.Cin >> 6) * 3 >= (1 << 15) || a.dmask_bits)) return 0;   // a.Cin: physical channels
+  if (dtype == FSR_X3 && ((a.Cin & 63) != 0 || (a.Cin >> 6) * 3 >= (1 << 15))) return 0;   // a.Cin: physical channels
   if (a.Cin < 64 || a.Cin % 32 != 0 || a.Cout % 64 != 0 || a.Cout < 64 || a.CoutPad != a.Cout) return 0;
   if (a.ps || a.in_ps || a.out_f32 || a.preact || a.oscale || a.bias || a.stats || a.pool2 || a.act != FSR_ACT_NONE || a.dmask_add) return 0;
   if (a.IH != (a.FOH - 1) / 2 + 1 || a.IW != (a.FOW - 1) / 2 + 1) return 0;

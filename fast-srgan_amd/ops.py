@@ -473,7 +473,7 @@ def conv3x3_raw(cd, x, wpk, cout, *, mode=L.CONV_FWD, out_hw=None, stride=1, bia
     dact_bits: `dact_mask` is the packed sign-bit tensor (N,OH,OW,Cout/8) uint8 of the producing layer's output (stride-2 data gradients)."""
     _check_dev(x)
     if cd.x3:
-        x, dact_mask = _aligned(x), (_aligned(dact_mask) if dact_mask is not None else None)
+        x, dact_mask = _aligned(x), (_aligned(dact_mask) if (dact_mask is not None and not dact_bits) else dact_mask)
     n = x.shape[0]
     if in_pixel_shuffled:
         ih, iw, cin = x.shape[1] // 2, x.shape[2] // 2, x.shape[3] * 4
@@ -605,7 +605,7 @@ class ConvCfg:
         # (model.py:69, :115).  Their gradients come back to THIS function's backward, whose data-gradient launch adds the
         # first one in its epilogue (fsr_conv_desc.mask_is_addend): autograd has nothing left to accumulate on the block input.
         self.n_alias = n_alias
-        # emit_signs (first-layer kernels, training, 16-bit): the forward also writes the SIGN BITS of its output (N,H,W,Cout/8 uint8)
+        # emit_signs (first-layer kernels, training, 16-bit and x3): the forward also writes the SIGN BITS of its output (N,H,W,Cout/8 uint8)
         # and hangs them on the output tensor (`_fsr_signs`); a stride-2 consumer with input_act_bwd then reads those -- a sixteenth
         # of the bytes -- as its activation-gradient mask instead of the tensor itself
         self.emit_signs = emit_signs
@@ -633,7 +633,7 @@ class Conv3x3Fn(torch.autograd.Function):
             return Conv3x3Fn._forward_c3(ctx, x, weight, bias, prelu, cfg)
         ctx.c3 = False
         # sign bits of the input (hung on it by the first-layer kernel that produced it): the stride-2 data gradient's mask
-        ctx.in_signs = getattr(x, "_fsr_signs", None) if (cfg.input_act_bwd is not None and cfg.stride == 2 and cd.is16) else None
+        ctx.in_signs = getattr(x, "_fsr_signs", None) if (cfg.input_act_bwd is not None and cfg.stride == 2 and (cd.is16 or cd.x3)) else None
         if cfg.image_in:
             xin = image_to_nhwc(cd, x, cfg.in_scale, cfg.in_shift)
         else:
@@ -690,7 +690,7 @@ class Conv3x3Fn(torch.autograd.Function):
         out = _empty((n, h, w, cout), cd.torch_dtype, x.device)
         pre = _empty_like(out) if want_pre else None
         signs = (torch.empty((n, h, w, cout // 8), dtype=torch.uint8, device=x.device)
-                 if (cfg.emit_signs and USE_SIGN_BITS and training and cd.is16 and cout % 64 == 0) else None)
+                 if (cfg.emit_signs and USE_SIGN_BITS and training and (cd.is16 or cd.x3) and cout % 64 == 0) else None)
         sn, sc, sh, sw = x.stride()
         prof = PROFILE_CONV
         if prof is not None:

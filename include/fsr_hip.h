@@ -137,7 +137,7 @@ typedef struct fsr_conv_desc {
   int out_f32;
   int pool2; /* FWD, 16-bit dtypes, no pixel shuffle: out is the MaxPool2d(2,2) of the activated result, [n,oh/2,ow/2,cout] */
   int mask_is_addend; /* 0: dact_mask gates the result by its sign; 1: it is ADDED to the result instead (see below); 2 (stride-2 data
-                         gradients, 16-bit dtypes): it is the PACKED SIGN-BIT tensor [n][oh][ow][cout / 8] of the producing layer's output
+                         gradients, 16-bit dtypes and FSR_X3): it is the PACKED SIGN-BIT tensor [n][oh][ow][cout / 8] of the producing layer's output
                          (bit c & 7 of byte c >> 3 = output > 0: fsr_conv3x3_c3_fwd's `signs`), gating like 0 at a sixteenth of the bytes */
   int pack_lin; /* 0: packed_w is fsr_pack_conv3x3's layout; 64 / 128: fsr_pack_conv3x3_lin's with that block (must equal fsr_conv3x3_pack_block) */
   int yuv_matrix;     /* FSR_OUT_I420: FSR_YUV_BT601 or FSR_YUV_BT709 (ignored by the other output kinds) */
@@ -308,8 +308,10 @@ int fsr_resample_image_yuv(const float* t, int n, int h, int w, int oh, int ow, 
  * cout must be a multiple of 16.
  *   fsr_pack_conv3x3_c3 : OIHW float [cout][3][3][3] -> `dtype` [round_up(cout,16)][32], k = (ky*3+kx)*3 + ci.
  *   fsr_conv3x3_c3_fwd  : out[n,h,w,cout] = act(conv + bias); act NONE/RELU/LEAKY/PRELU; preact optional; signs optional (16-bit
- *                         dtypes, cout % 64 == 0): uint8 [n,h,w,cout/8], bit c & 7 of byte c >> 3 = (out[..., c] > 0) -- the activation-gradient
- *                         mask of the layer as fsr_conv3x3's mask_is_addend = 2 reads it.
+ *                         dtypes and FSR_X3, cout % 64 == 0): uint8 [n,h,w,cout/8], bit c & 7 of byte c >> 3 = (out[..., c] > 0; FSR_X3:
+ *                         the stored hi part > 0, the predicate the tensor mask applies) -- the activation-gradient mask of the layer as
+ *                         fsr_conv3x3's mask_is_addend = 2 reads it.  The forward works in strips of 16, 32 or 64 rows (chosen per shape;
+ *                         environment FSR_C3_ROWS = 16 | 32 | 64 forces one): results do not depend on the height.
  *   fsr_conv3x3_c3_wgrad: dw_oihw (float [cout][3][3][3]) += d loss / d weight for dz [n,h,w,cout] `dtype`;
  *                         dbias (optional, float [cout]) += per-channel sums of dz (the bias gradient: a column of
  *                         ones in the padded K dimension of the same MFMAs);
