@@ -16,12 +16,13 @@ FSR_F32, FSR_BF16, FSR_F16, FSR_X3 = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU, ACT_TANH = 0, 1, 2, 3, 4
 CONV_FWD, CONV_DGRAD = 0, 1
 PACK_FWD, PACK_FWD_PS, PACK_DGRAD, PACK_DGRAD_PS = 0, 1, 2, 3
-OUT_DTYPE, OUT_F32, OUT_U8, OUT_I420 = 0, 1, 2, 3
+OUT_DTYPE, OUT_F32, OUT_U8, OUT_I420, OUT_NV12 = 0, 1, 2, 3, 4
 YUV_BT601, YUV_BT709 = 0, 1                 # fsr_conv_desc.yuv_matrix, fsr_i420_to_image
 SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_image's input
 CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr_*_yuv entry points
+LAYOUT_PLANAR, LAYOUT_NV12 = 0, 1                # payload layout of the fsr_*_yuv_ex entry points
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
 
@@ -81,6 +82,10 @@ SIGNATURES = {
     "fsr_yuv_to_image": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_image_to_yuv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "fsr_resample_image_yuv": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_yuv_to_image_ex": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "fsr_image_to_yuv_ex": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_resample_image_yuv_ex": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          P, P]),
     "fsr_resample_image": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "fsr_pack_conv3x3_c3": (c_int, [c_int, P, c_int, P, c_int, P]),
     "fsr_tanh_bwd_image": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_int, c_int, c_int, P, P, P, P]),

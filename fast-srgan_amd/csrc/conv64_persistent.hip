@@ -206,8 +206,9 @@ __global__ __launch_bounds__(NTHR64, 2) void conv64_thin_kernel(const ConvKArgs 
       const int ty = rem / a.tiles_x, tx = rem - ty * a.tiles_x;
       const int gx = tx * 16 + l15, gyb = ty * 16 + wave * 2;
       const bool col_ok = gx < a.GW;
-      if (a.out_f32 == FSR_OUT_I420) {
-        // I420 planes of the RGB head (Cout = 3, tanh, even FOH / FOW: host checked).  The wave's rows gyb, gyb + 1 (gyb even) and
+      if (a.out_f32 >= FSR_OUT_I420) {
+        // I420 planes of the RGB head (Cout = 3, tanh, even FOH / FOW: host checked; FSR_OUT_NV12: the same codes as the NV12
+        // payload, one plane of (Cb, Cr) pairs -- i420_store_chroma).  The wave's rows gyb, gyb + 1 (gyb even) and
         // the columns of lanes l15, l15 ^ 1 are one 2x2 chroma block: every lane takes part in the shuffle, lane group 0 (channels
         // 0 .. 2) stores -- two Y samples per lane, the block's Cb / Cr from the even column.  Partial tiles: an even GW / GH keeps
         // both columns / rows of a block on the same side of the border.
@@ -223,11 +224,7 @@ __global__ __launch_bounds__(NTHR64, 2) void conv64_thin_kernel(const ConvKArgs 
           unsigned char* o = (unsigned char*)a.out + (size_t)img * (plane + 2 * cplane);
           o[(size_t)gyb * a.FOW + gx] = yv[0];
           o[(size_t)(gyb + 1) * a.FOW + gx] = yv[1];
-          if (!(l15 & 1)) {
-            const size_t c = (size_t)(gyb >> 1) * (a.FOW >> 1) + (gx >> 1);
-            o[plane + c] = cb;
-            o[plane + cplane + c] = cr;
-          }
+          if (!(l15 & 1)) i420_store_chroma(o, plane, a.FOW, gyb, gx, cb, cr, a.out_f32 == FSR_OUT_NV12);
         }
       } else {
         // float output, Cout <= 16 valid channels (lane group lg holds channels 4 lg .. 4 lg + 3): scale, bias, tanh / slope
@@ -912,7 +909,9 @@ int fsr_conv64_persistent_try(int dtype, ConvKArgs& a, int S, hipStream_t stream
     else if (a.dmask) hipLaunchKernelGGL((conv64_v2_kernel<bf16_t, false, true>), dim3(grid), dim3(NTHR64), LDS64V2, stream, a);
     else hipLaunchKernelGGL((conv64_v2_kernel<bf16_t, false, false>), dim3(grid), dim3(NTHR64), LDS64V2, stream, a);
   }
-  fsr_note_kernel(x3 ? "conv64_thin_kernel<x3>" : (thin ? "conv64_thin_kernel" : "conv64_v2_kernel"));
+  const bool nv12 = a.out_f32 == FSR_OUT_NV12;     // (thin only) named apart from the planar head
+  fsr_note_kernel(x3 ? (nv12 ? "conv64_thin_kernel<x3>[nv12]" : "conv64_thin_kernel<x3>")
+                     : (thin ? (nv12 ? "conv64_thin_kernel[nv12]" : "conv64_thin_kernel") : "conv64_v2_kernel"));
   int rc = fsr_check_launch(thin ? "conv64_thin_kernel" : "conv64_v2_kernel");
   return rc ? rc : 1;
 }

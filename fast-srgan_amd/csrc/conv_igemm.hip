@@ -517,8 +517,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvK
   if (BN == 16 && ((a.out_f32 && sizeof(T) == 2) || a.Cout % 16 != 0 || a.out_f32 == FSR_OUT_U8)) {  // only the 16-wide configs carry this code
     // ---- thin / float path (memory-bound layers): per-element guards, optional scale, tanh
     if constexpr (MT % 2 == 0 && NT == 1 && S == 1) {   // (launch_cfg refuses FSR_OUT_I420 for every other configuration)
-      if (a.out_f32 == FSR_OUT_I420) {
-        // I420 planes of the RGB head (Cout = 3, tanh, forward, even FOH / FOW: host checked): rows gyb + 2 k, gyb + 2 k + 1 of the
+      if (a.out_f32 >= FSR_OUT_I420) {
+        // I420 planes of the RGB head (Cout = 3, tanh, forward, even FOH / FOW: host checked; FSR_OUT_NV12: the same codes as the
+        // NV12 payload, one plane of (Cb, Cr) pairs -- i420_store_chroma): rows gyb + 2 k, gyb + 2 k + 1 of the
         // wave (gy0 = ty * TH and gyb are even) and the columns of lanes l15, l15 ^ 1 are one 2x2 chroma block.  Every lane shuffles,
         // lane group 0 (channels 0 .. 2) stores; an even GW / GH keeps a block on one side of a partial tile's border.
         const size_t plane = (size_t)a.FOH * a.FOW, cplane = plane >> 2;
@@ -540,11 +541,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_igemm_kernel(const ConvK
           if (lg == 0 && col_ok && gy < a.GH) {
             o[(size_t)gy * a.FOW + gx] = yv[0];
             o[(size_t)(gy + 1) * a.FOW + gx] = yv[1];
-            if (!(l15 & 1)) {
-              const size_t c = (size_t)(gy >> 1) * (a.FOW >> 1) + (gx >> 1);
-              o[plane + c] = cb;
-              o[plane + cplane + c] = cr;
-            }
+            if (!(l15 & 1)) i420_store_chroma(o, plane, a.FOW, gy, gx, cb, cr, a.out_f32 == FSR_OUT_NV12);
           }
         });
         return;
@@ -733,10 +730,11 @@ static int launch_cfg(ConvKArgs& a, hipStream_t stream, ConvKArgs* more = nullpt
   if (a.in_ps && (a.Cin / 4) % KC != 0)
     return fsr_fail(-2, "conv3x3: pixel-shuffled input needs (Cin/4)=%d to be a multiple of the chunk %d", a.Cin / 4, KC);
   if (a.CoutPad % BN != 0) return fsr_fail(-2, "conv3x3: padded Cout=%d is not a multiple of %d", a.CoutPad, BN);
-  // FSR_OUT_I420 is stored by the thin epilogue of the stride-1 configurations, whose waves must hold whole 2x2 blocks: an even
+  // FSR_OUT_I420 (and FSR_OUT_NV12, the same epilogue) is stored by the thin epilogue of the stride-1 configurations, whose waves
+  // must hold whole 2x2 blocks: an even
   // number of rows per wave (rows gy0 + wm * MT + m with an even tile height) and one 16-column tile per wave (lanes l15, l15 ^ 1
   // are neighbouring columns).  Of the configurations that serve a thin (CoutPad = 16) head only <8, 16, 4, 1> exists: MT = 2.
-  if (a.out_f32 == FSR_OUT_I420 && (S != 1 || BN != 16 || TH % 2 != 0 || (TH / WM) % 2 != 0 || BN / 16 / WN != 1 || nmore > 0 ||
+  if (a.out_f32 >= FSR_OUT_I420 && (S != 1 || BN != 16 || TH % 2 != 0 || (TH / WM) % 2 != 0 || BN / 16 / WN != 1 || nmore > 0 ||
                                     a.osy != 1 || a.osx != 1 || a.ooy != 0 || a.oox != 0))
     return fsr_fail(-2, "conv3x3: I420 output: configuration <TH=%d, BN=%d, WM=%d, WN=%d, S=%d> would split a 2x2 block between waves",
                     TH, BN, WM, WN, S);
@@ -777,7 +775,8 @@ static int launch_cfg(ConvKArgs& a, hipStream_t stream, ConvKArgs* more = nullpt
     attr_set = true;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(WM * WN * 64), lds, stream, a, cls);
-  fsr_note_kernel("conv_igemm_kernel<%s,%d,%d,%d,%d,%d,%d,%d,%d>", X3 ? "x3" : (sizeof(T) == 4 ? "f32" : (std::is_same<T, f16_t>::value ? "f16" : "bf16")), TH, BN, WM, WN, KC, S, G, DMA);
+  fsr_note_kernel("conv_igemm_kernel<%s,%d,%d,%d,%d,%d,%d,%d,%d>%s", X3 ? "x3" : (sizeof(T) == 4 ? "f32" : (std::is_same<T, f16_t>::value ? "f16" : "bf16")), TH, BN, WM, WN, KC, S, G, DMA,
+                  a.out_f32 == FSR_OUT_NV12 ? "[nv12]" : "");   // (the NV12 head: named apart from the planar one)
   return fsr_check_launch("conv_igemm_kernel");
 }
 

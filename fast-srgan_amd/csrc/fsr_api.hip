@@ -147,10 +147,10 @@ static int conv3x3_impl(const fsr_conv_desc* d, const void* in, const void* pack
                    dact_mask || oscale || (d->oh & 1) || (d->ow & 1) || d->cout % 16 != 0 || d->act == FSR_ACT_TANH))
     return fsr_fail(-2, "fsr_conv3x3: pool2 is for stride-1 forward launches of the 16-bit modes with even output extents "
                         "(no statistics / pre-activation / mask / scale tensors, no pixel shuffle)");
-  if (d->out_f32 < 0 || d->out_f32 > FSR_OUT_I420) return fsr_fail(-2, "fsr_conv3x3: unknown output kind %d", d->out_f32);
+  if (d->out_f32 < 0 || d->out_f32 > FSR_OUT_NV12) return fsr_fail(-2, "fsr_conv3x3: unknown output kind %d", d->out_f32);
   if (d->out_f32 == FSR_OUT_U8 && (d->act != FSR_ACT_TANH || d->cout > 16 || d->pixel_shuffle || d->mode != FSR_CONV_FWD))
     return fsr_fail(-2, "fsr_conv3x3: uint8 image output is for tanh heads (forward, cout <= 16)");
-  if (d->out_f32 == FSR_OUT_I420) {
+  if (d->out_f32 == FSR_OUT_I420 || d->out_f32 == FSR_OUT_NV12) {   // (NV12: the same epilogue, the same conditions and messages)
     // the conditions of FSR_OUT_U8, three (RGB) channels, whole 2x2 chroma blocks, and none of the optional tensors the thin
     // epilogues would otherwise read or write per channel
     if (d->act != FSR_ACT_TANH || d->cout != 3 || d->pixel_shuffle || d->mode != FSR_CONV_FWD || d->stride != 1 || stats || preact ||

@@ -41,7 +41,8 @@ struct ConvKArgs {
   int ps;               // epilogue stores depth-to-space(2); weight rows packed [q][c]
   int in_ps;            // `in` is stored depth-to-space(2) (gradient of a pixel-shuffle conv)
   int out_f32;          // 1: store float regardless of T;  2 (FSR_OUT_U8): store the uint8 image of a tanh head;
-                        // 3 (FSR_OUT_I420): store the I420 planes of a 3-channel tanh head (i420_quad, fsr_yuv.h)
+                        // 3 (FSR_OUT_I420): store the I420 planes of a 3-channel tanh head (i420_quad, fsr_yuv.h);
+                        // 4 (FSR_OUT_NV12): the same codes as the NV12 payload (i420_store_chroma)
   int yuv_matrix, yuv_full;   // FSR_OUT_I420: FSR_YUV_BT601 / FSR_YUV_BT709, limited (0) / full (1) range
   int pool2;            // epilogue stores MaxPool2d(2,2) of the activated result ([N][FOH/2][FOW/2][Cout]) instead of the result
   int tiles_x, tiles_y, nblk_n;

@@ -16,6 +16,7 @@ void fsr_note_kernel(const char* fmt, ...);
 // Planar-YUV output of h x w (yuv.hip; the encode entry points and the resampler): 4:2:0 needs even extents, 4:2:2 an even width, and
 // the matrix / range pair must be known.  0, or the refusal recorded in `who`'s name (`what`: a word put in front of the colour message).
 int fsr_yuv_out_check(const char* who, const char* what, int chroma, int h, int w, int matrix, int full_range);
+int fsr_yuv_layout_check(const char* who, int chroma, int layout);   // yuv.hip: a known payload layout, semi-planar with 4:2:0 only
 
 int fsr_conv_igemm_dispatch(int dtype, ConvKArgs& a, int S, hipStream_t stream);
 // `n` launches that differ only in output grid / taps / output offset (stride-2 data-gradient classes) as ONE launch

@@ -60,6 +60,25 @@ __device__ __forceinline__ void i420_quad(const float (&t)[2][3], int matrix, in
   sr += __shfl_xor(sr, 1, 64);
   i420_chroma(k, sb, sr, cb, cr);
 }
+// The chroma store of the even-column lane of a block at rows gy, gy + 1 (gy even), column gx (even) of an 8-bit frame `o` of fow
+// columns whose Y plane holds `plane` bytes: one byte into each of the Cb and Cr planes (FSR_OUT_I420), or -- nv12: FSR_OUT_NV12,
+// DESIGN.md §6f -- the (Cb, Cr) pair into the one chroma plane of fow bytes per row, as one 2-byte store where the address allows.
+__device__ __forceinline__ void i420_store_chroma(unsigned char* o, size_t plane, int fow, int gy, int gx, unsigned char cb, unsigned char cr,
+                                                  bool nv12) {
+  if (nv12) {
+    unsigned char* q = o + plane + (size_t)(gy >> 1) * fow + gx;
+    if (((size_t)q & 1) == 0) {
+      *(unsigned short*)q = (unsigned short)((unsigned)cb | ((unsigned)cr << 8));
+    } else {
+      q[0] = cb;
+      q[1] = cr;
+    }
+  } else {
+    const size_t c = (size_t)(gy >> 1) * (fow >> 1) + (gx >> 1);
+    o[plane + c] = cb;
+    o[plane + (plane >> 2) + c] = cr;
+  }
+}
 
 // ---- I420 planes from a thread that holds 4 columns x 2 rows -- two whole 2x2 blocks, no shuffle (the resampler's I420 stage and
 // fsr_image_to_i420).  C = unsigned char (8-bit samples) or unsigned short (9..16 bits, little-endian, the value in the low bits).
@@ -84,9 +103,12 @@ __device__ __forceinline__ void store_codes4(C* p, const C (&b)[4], int count) {
 }
 // v[m][3 c + ch]: clamped (R, G, B) in [0, 1] of row yo + m, column xg + c of a frame of oh x ow (both even; yo, xg even); cnt = 2 or 4
 // valid columns.  Per column the vertical pair first, then the two columns of a block (i420_quad's order of the chroma sum).
-template <typename C>
+// SEMI: the semi-planar payload -- the same codes, shifted left by sh = 16 - depth for 16-bit samples (the code in the
+// HIGH bits: P010, P012, P016; sh = 0 for NV12's bytes), Cb0, Cr0, Cb1, Cr1 into the one chroma plane of ow samples per row as ONE
+// store_codes4 where the planar form makes 2 + 2 stores.
+template <typename C, bool SEMI = false>
 __device__ __forceinline__ void i420_store_2x4(const i420_coef& kc, const float (&v)[2][12], C* frame, int oh, int ow, int yo, int xg,
-                                               int cnt) {
+                                               int cnt, int sh = 0) {
   const size_t plane = (size_t)oh * ow, cw = (size_t)(ow >> 1), cplane = (size_t)(oh >> 1) * cw;
   C yv[2][4], cb[2], cr[2];
   float sb[4], sr[4];
@@ -104,6 +126,18 @@ __device__ __forceinline__ void i420_store_2x4(const i420_coef& kc, const float 
   }
 #pragma unroll
   for (int p = 0; p < 2; ++p) i420_chroma(kc, sb[2 * p] + sb[2 * p + 1], sr[2 * p] + sr[2 * p + 1], cb[p], cr[p]);
+  if constexpr (SEMI) {
+    C cc[4] = {(C)(cb[0] << sh), (C)(cr[0] << sh), (C)(cb[1] << sh), (C)(cr[1] << sh)};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      yv[0][c] = (C)(yv[0][c] << sh);
+      yv[1][c] = (C)(yv[1][c] << sh);
+    }
+    store_codes4(frame + (size_t)yo * ow + xg, yv[0], cnt);
+    store_codes4(frame + (size_t)(yo + 1) * ow + xg, yv[1], cnt);
+    store_codes4(frame + plane + (size_t)(yo >> 1) * ow + xg, cc, cnt);   // (cnt = 2: one pair, cnt = 4: two)
+    return;
+  }
   store_codes4(frame + (size_t)yo * ow + xg, yv[0], cnt);
   store_codes4(frame + (size_t)(yo + 1) * ow + xg, yv[1], cnt);
   C* c0 = frame + plane + (size_t)(yo >> 1) * cw + (xg >> 1);

@@ -31,6 +31,7 @@ constexpr int RS_LDS_BUDGET = 64 * 1024;   // bytes of dynamic LDS a workgroup m
 constexpr int RS_MAX_RATIO = 8;            // supported down-scaling ratio per axis (tap rows of up to 33)
 // template kinds of the planar 4:2:2 / 4:4:4 stages, next to the FSR_OUT_* values of the public kinds
 constexpr int RS_YUV422 = 8 + FSR_CHROMA_422, RS_YUV444 = 8 + FSR_CHROMA_444;
+constexpr int RS_NV12 = 12;                // the I420 stage storing the semi-planar payload (FSR_LAYOUT_NV12)
 constexpr int rs_rowf(int kind) { return kind == RS_YUV422 ? RS_ROWF + 4 : RS_ROWF; }   // floats of one LDS row: 4:2:2 keeps a 65th column
 
 struct ResampleArgs {
@@ -58,7 +59,8 @@ __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 
 
 // KIND: FSR_OUT_F32 / FSR_OUT_U8 / FSR_OUT_I420.  KXS = 5 / 9: rows of at most 5 (every up-scale) / 9 (down-scales up to 2: the
 // network's 4x taken to 3x or 2x of the input) horizontal taps, held in registers; KXS = 0: any tap count, read per use.
-// C (FSR_OUT_I420, RS_YUV422, RS_YUV444): the sample type of the planes -- unsigned char, or unsigned short for 9..16-bit samples (a.depth).
+// RS_NV12: FSR_OUT_I420's stage with the semi-planar store (16-bit codes in the high bits).
+// C (FSR_OUT_I420, RS_NV12, RS_YUV422, RS_YUV444): the sample type of the planes -- unsigned char, or unsigned short for 9..16-bit samples (a.depth).
 template <int KIND, int KXS, typename C = unsigned char>
 __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
   HIP_DYNAMIC_SHARED(float, lds)
@@ -214,7 +216,8 @@ __global__ __launch_bounds__(256) void resample_kernel(const ResampleArgs a) {
         }
       }
       // the lane's columns xl .. xl + 3 are two 2x2 blocks; cnt = 2 or 4: ow and the tile origin are even
-      i420_store_2x4<C>(kc, v, frame, a.oh, a.ow, y0 + 2 * rp, x0 + xl, imin(4, tw - xl));
+      i420_store_2x4<C, KIND == RS_NV12>(kc, v, frame, a.oh, a.ow, y0 + 2 * rp, x0 + xl, imin(4, tw - xl),
+                                         KIND == RS_NV12 && sizeof(C) == 2 ? 16 - a.depth : 0);
     }
   }
 }
@@ -249,6 +252,7 @@ void launch_kind(const ResampleArgs& a, long long grid, size_t lds_bytes, hipStr
 template <typename C>
 void launch_planar(int kind, const ResampleArgs& a, long long grid, size_t lds_bytes, hipStream_t stream) {
   if (kind == FSR_OUT_I420) launch_kind<FSR_OUT_I420, C>(a, grid, lds_bytes, stream);
+  else if (kind == RS_NV12) launch_kind<RS_NV12, C>(a, grid, lds_bytes, stream);
   else if (kind == RS_YUV422) launch_kind<RS_YUV422, C>(a, grid, lds_bytes, stream);
   else launch_kind<RS_YUV444, C>(a, grid, lds_bytes, stream);
 }
@@ -257,7 +261,7 @@ void launch_planar(int kind, const ResampleArgs& a, long long grid, size_t lds_b
 // for 16-bit samples (fsr_resample_image_i420_deep, fsr_resample_image_yuv)
 int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
                     const float* wx, const int* xmin, const int* xsize, int kx, int out_kind, int chroma, int yuv_matrix, int yuv_full_range,
-                    int depth, void* out, fsr_stream_t stream_) {
+                    int depth, void* out, fsr_stream_t stream_, int layout = FSR_LAYOUT_PLANAR) {
   if (!t || !wy || !ymin || !ysize || !wx || !xmin || !xsize || !out) return fsr_fail(-1, "fsr_resample_image: null argument");
   if (n <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0 || ky <= 0 || kx <= 0)
     return fsr_fail(-2, "fsr_resample_image: bad sizes (n %d, %d x %d -> %d x %d, taps %d x %d)", n, h, w, oh, ow, ky, kx);
@@ -270,7 +274,8 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
   if ((long long)h > (long long)RS_MAX_RATIO * oh || (long long)w > (long long)RS_MAX_RATIO * ow)
     return fsr_fail(-2, "fsr_resample_image: down-scaling ratio %.3f x %.3f (%d x %d -> %d x %d) is beyond the supported %d", (double)h / oh,
                     (double)w / ow, h, w, oh, ow, RS_MAX_RATIO);
-  const int kind = out_kind == FSR_OUT_I420 && chroma != FSR_CHROMA_420 ? 8 + chroma : out_kind;   // the kernel's KIND
+  // the kernel's KIND (FSR_LAYOUT_NV12 comes with FSR_OUT_I420 and 4:2:0 only: fsr_resample_image_yuv_ex has seen to it)
+  const int kind = out_kind == FSR_OUT_I420 && chroma != FSR_CHROMA_420 ? 8 + chroma : (layout == FSR_LAYOUT_NV12 ? RS_NV12 : out_kind);
   const int rowf = rs_rowf(kind);
   int th = 32, rows = 0;
   for (;; th >>= 1) {
@@ -299,7 +304,7 @@ int resample_launch(const float* t, int n, int h, int w, int oh, int ow, const f
   else if (kind == FSR_OUT_U8) launch_kind<FSR_OUT_U8>(a, grid, lds_bytes, stream);
   else if (depth == 8) launch_planar<unsigned char>(kind, a, grid, lds_bytes, stream);
   else launch_planar<unsigned short>(kind, a, grid, lds_bytes, stream);
-  const char* name = kind == FSR_OUT_F32 ? "f32" : kind == FSR_OUT_U8 ? "u8" : kind == FSR_OUT_I420 ? "i420" : kind == RS_YUV422 ? "yuv422" : "yuv444";
+  const char* name = kind == FSR_OUT_F32 ? "f32" : kind == FSR_OUT_U8 ? "u8" : kind == FSR_OUT_I420 ? "i420" : kind == RS_NV12 ? "nv12" : kind == RS_YUV422 ? "yuv422" : "yuv444";
   // the sample type: named for 16-bit samples, and for the 4:2:2 / 4:4:4 planes at either
   fsr_note_kernel("resample_kernel<%s,%d%s>", name, kx <= 5 ? 5 : (kx <= 9 ? 9 : 0), depth != 8 ? ",u16" : (kind > FSR_OUT_I420 ? ",u8" : ""));
   return fsr_check_launch("resample_kernel");
@@ -331,4 +336,17 @@ extern "C" int fsr_resample_image_yuv(const float* t, int n, int h, int w, int o
     return fsr_fail(-2, "fsr_resample_image_yuv: the payloads of 16-bit samples must be 2-byte aligned");
   return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, chroma, yuv_matrix, yuv_full_range, depth, out,
                          stream_);
+}
+
+extern "C" int fsr_resample_image_yuv_ex(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize,
+                                         int ky, const float* wx, const int* xmin, const int* xsize, int kx, int chroma, int layout,
+                                         int yuv_matrix, int yuv_full_range, int depth, void* out, fsr_stream_t stream_) {
+  if (chroma != FSR_CHROMA_420 && chroma != FSR_CHROMA_422 && chroma != FSR_CHROMA_444)
+    return fsr_fail(-2, "fsr_resample_image_yuv_ex: unknown chroma subsampling %d", chroma);
+  if (int rc = fsr_yuv_layout_check("fsr_resample_image_yuv_ex", chroma, layout)) return rc;
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_resample_image_yuv_ex: depth %d is outside 8..16", depth);
+  if (depth > 8 && ((size_t)out & 1) != 0)
+    return fsr_fail(-2, "fsr_resample_image_yuv_ex: the payloads of 16-bit samples must be 2-byte aligned");
+  return resample_launch(t, n, h, w, oh, ow, wy, ymin, ysize, ky, wx, xmin, xsize, kx, FSR_OUT_I420, chroma, yuv_matrix, yuv_full_range, depth, out,
+                         stream_, layout);
 }

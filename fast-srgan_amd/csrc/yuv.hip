@@ -1,6 +1,7 @@
 // Planar YUV frames in and out of the generator's float image (the colour contract is DESIGN.md §6c): the decode and encode kernels of
 // 4:2:0, 4:2:2 and 4:4:4 payloads at 8 to 16 bits, and their five entry points.  fsr_yuv_to_image and fsr_image_to_yuv are the
-// implementation; the I420-named entry points forward into them.  The arithmetic lives in fsr_yuv.h, shared with the head kernels'
+// implementation; the I420-named entry points forward into them, and the _ex forms add the payload layout: FSR_LAYOUT_NV12, the
+// semi-planar 4:2:0 payload of DESIGN.md §6f (NV12, P010, P012, P016).  The arithmetic lives in fsr_yuv.h, shared with the head kernels'
 // I420 epilogue and with the resampler (resample.hip), which also shares fsr_yuv_out_check below.
 #include "fsr_yuv.h"
 #include "fsr_host.h"
@@ -15,10 +16,13 @@ namespace {
 // value in the low `depth` bits; a stored value above 2^depth - 1 is taken as it is, the clamp of R, G, B deals with it).  The
 // coefficients scale with the depth: limited Y = (16 + 219 E_Y) 2^(d-8), C = (128 + 224 E_C) 2^(d-8); full Y = (2^d - 1) E_Y,
 // C = 2^(d-1) + (2^d - 1) E_C -- for S = unsigned char d is the constant 8.
-template <typename S>
+// SEMI (FSR_LAYOUT_NV12): the chroma planes are ONE plane of ch rows of cw (Cb, Cr) pairs -- pair stride 2, Cr at + 1 --, and a 16-bit
+// sample holds its code in the HIGH d bits: every sample read is stored >> (16 - d), whatever the low bits hold.  Same arithmetic.
+template <typename S, bool SEMI = false>
 __global__ __launch_bounds__(256) void i420_to_image_kernel(const S* __restrict__ src, float* __restrict__ dst, int n, int h,
                                                             int w, int mpeg2, int matrix, int full, int depth) {
   const int d = sizeof(S) == 1 ? 8 : depth;
+  const int sh = SEMI && sizeof(S) == 2 ? 16 - d : 0;
   const int ch = (h + 1) >> 1, cw = (w + 1) >> 1;
   const long long plane = (long long)h * w, cplane = (long long)ch * cw, fbytes = plane + 2 * cplane;   // (samples)
   const i420_coef kc = yuv_decode_coefs(matrix, full, d);
@@ -35,12 +39,25 @@ __global__ __launch_bounds__(256) void i420_to_image_kernel(const S* __restrict_
     float c[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      const S* q = f + plane + k * cplane;
-      const float top = (1.f - fx) * (float)q[y0 * cw + x0] + fx * (float)q[y0 * cw + x1];
-      const float bot = (1.f - fx) * (float)q[y1 * cw + x0] + fx * (float)q[y1 * cw + x1];
+      float s00, s01, s10, s11;
+      if constexpr (SEMI) {
+        const S* q = f + plane + k;
+        s00 = (float)(q[2 * ((long long)y0 * cw + x0)] >> sh);
+        s01 = (float)(q[2 * ((long long)y0 * cw + x1)] >> sh);
+        s10 = (float)(q[2 * ((long long)y1 * cw + x0)] >> sh);
+        s11 = (float)(q[2 * ((long long)y1 * cw + x1)] >> sh);
+      } else {
+        const S* q = f + plane + k * cplane;
+        s00 = (float)q[y0 * cw + x0];
+        s01 = (float)q[y0 * cw + x1];
+        s10 = (float)q[y1 * cw + x0];
+        s11 = (float)q[y1 * cw + x1];
+      }
+      const float top = (1.f - fx) * s00 + fx * s01;
+      const float bot = (1.f - fx) * s10 + fx * s11;
       c[k] = (1.f - fy) * top + fy * bot;
     }
-    yuv_decode_pixel(kc, (float)f[p], c[0], c[1], dst + i * 3);
+    yuv_decode_pixel(kc, SEMI ? (float)(f[p] >> sh) : (float)f[p], c[0], c[1], dst + i * 3);
   }
 }
 
@@ -51,7 +68,8 @@ __global__ __launch_bounds__(256) void i420_to_image_kernel(const S* __restrict_
 // 4- or 8-byte Y store per row and 2 + 2 chroma samples.  Grid-stride over the n * (h / 2) * ceil(w / 4) units (< 2^31: host checked).
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-template <typename C>
+// SEMI (FSR_LAYOUT_NV12): the semi-planar payload -- the unit's Cb0, Cr0, Cb1, Cr1 leave as one store, 16-bit codes in the high bits
+template <typename C, bool SEMI = false>
 __global__ __launch_bounds__(256) void image_to_i420_kernel(const float* __restrict__ t, C* __restrict__ out, int n, int h, int w, int matrix,
                                                             int full, int depth) {
   const i420_coef kc = i420_coefs(matrix, full, sizeof(C) == 1 ? 8 : depth);
@@ -82,7 +100,7 @@ __global__ __launch_bounds__(256) void image_to_i420_kernel(const float* __restr
         v[m][8 + k] = fminf(fmaxf((q2[k] + 1.f) / 2.f, 0.f), 1.f);
       }
     }
-    i420_store_2x4<C>(kc, v, out + (size_t)img * fsamples, h, w, y, x, cnt);
+    i420_store_2x4<C, SEMI>(kc, v, out + (size_t)img * fsamples, h, w, y, x, cnt, SEMI && sizeof(C) == 2 ? 16 - depth : 0);
   }
 }
 
@@ -223,27 +241,34 @@ int decode_check(const char* who, const void* frames, const float* img, int n, i
   return 0;
 }
 template <typename S>
-void decode_kernel(int chroma, unsigned blocks, hipStream_t stream, const void* frames, float* img, int n, int h, int w, int mpeg2,
+void decode_kernel(int chroma, int layout, unsigned blocks, hipStream_t stream, const void* frames, float* img, int n, int h, int w, int mpeg2,
                    int matrix, int full_range, int depth) {
   const dim3 grid(blocks), block(256);
   const S* src = (const S*)frames;
-  if (chroma == FSR_CHROMA_420)
+  if (layout == FSR_LAYOUT_NV12)      // (4:2:0: the entry point has seen to it)
+    hipLaunchKernelGGL((i420_to_image_kernel<S, true>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
+  else if (chroma == FSR_CHROMA_420)
     hipLaunchKernelGGL(i420_to_image_kernel<S>, grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
   else if (chroma == FSR_CHROMA_422)
     hipLaunchKernelGGL((yuv_to_image_kernel<S, FSR_CHROMA_422>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
   else
     hipLaunchKernelGGL((yuv_to_image_kernel<S, FSR_CHROMA_444>), grid, block, 0, stream, src, img, n, h, w, mpeg2, matrix, full_range, depth);
 }
-// chroma is one of the three, depth in 8..16 and a 16-bit payload 2-byte aligned: the entry points have seen to it
+// chroma is one of the three, depth in 8..16 and a 16-bit payload 2-byte aligned; layout FSR_LAYOUT_NV12 comes with 4:2:0 only: the
+// entry points have seen to it
 int yuv_to_image_launch(const char* who, const void* frames, float* img, int n, int h, int w, int chroma, int siting, int matrix,
-                        int full_range, int depth, fsr_stream_t stream_) {
+                        int full_range, int depth, fsr_stream_t stream_, int layout = FSR_LAYOUT_PLANAR) {
   const bool c420 = chroma == FSR_CHROMA_420, deep = depth > 8;
   if (chroma == FSR_CHROMA_444) siting = FSR_SITING_JPEG;   // (no interpolation: ignored)
   if (int rc = decode_check(who, frames, img, n, h, w, chroma, siting, matrix, full_range)) return rc;
   const unsigned blocks = capped_blocks(c420 ? (long long)n * h * w : (long long)n * h * ((w + 3) / 4));
   const int mpeg2 = siting == FSR_SITING_MPEG2 ? 1 : 0;
-  (deep ? decode_kernel<unsigned short> : decode_kernel<unsigned char>)(chroma, blocks, (hipStream_t)stream_, frames, img, n, h, w, mpeg2,
+  (deep ? decode_kernel<unsigned short> : decode_kernel<unsigned char>)(chroma, layout, blocks, (hipStream_t)stream_, frames, img, n, h, w, mpeg2,
                                                                         matrix, full_range, depth);
+  if (layout == FSR_LAYOUT_NV12) {
+    fsr_note_kernel("nv12_to_image_kernel<%s>", deep ? "u16" : "u8");
+    return fsr_check_launch("nv12_to_image_kernel");
+  }
   if (!c420) {
     fsr_note_kernel("yuv_to_image_kernel<%s,%s>", deep ? "u16" : "u8", chroma == FSR_CHROMA_422 ? "422" : "444");
     return fsr_check_launch("yuv_to_image_kernel");
@@ -264,24 +289,30 @@ int encode_check(const char* who, const float* t, const void* out, int n, int h,
   return 0;
 }
 template <typename C>
-void encode_kernel(int chroma, unsigned blocks, hipStream_t stream, const float* t, void* out, int n, int h, int w, int matrix, int full_range,
-                   int depth) {
+void encode_kernel(int chroma, int layout, unsigned blocks, hipStream_t stream, const float* t, void* out, int n, int h, int w, int matrix,
+                   int full_range, int depth) {
   const dim3 grid(blocks), block(256);
-  if (chroma == FSR_CHROMA_420)
+  if (layout == FSR_LAYOUT_NV12)      // (4:2:0: the entry point has seen to it)
+    hipLaunchKernelGGL((image_to_i420_kernel<C, true>), grid, block, 0, stream, t, (C*)out, n, h, w, matrix, full_range, depth);
+  else if (chroma == FSR_CHROMA_420)
     hipLaunchKernelGGL(image_to_i420_kernel<C>, grid, block, 0, stream, t, (C*)out, n, h, w, matrix, full_range, depth);
   else if (chroma == FSR_CHROMA_422)
     hipLaunchKernelGGL((image_to_yuv_kernel<C, FSR_CHROMA_422>), grid, block, 0, stream, t, (C*)out, n, h, w, matrix, full_range, depth);
   else
     hipLaunchKernelGGL((image_to_yuv_kernel<C, FSR_CHROMA_444>), grid, block, 0, stream, t, (C*)out, n, h, w, matrix, full_range, depth);
 }
-// chroma is one of the three
+// chroma is one of the three; layout FSR_LAYOUT_NV12 comes with 4:2:0 only
 int image_to_yuv_launch(const char* who, const float* t, int n, int h, int w, int chroma, int matrix, int full_range, int depth, void* out,
-                        fsr_stream_t stream_) {
+                        fsr_stream_t stream_, int layout = FSR_LAYOUT_PLANAR) {
   const bool c420 = chroma == FSR_CHROMA_420, deep = depth > 8;
   if (int rc = encode_check(who, t, out, n, h, w, chroma, matrix, full_range, depth)) return rc;
   const unsigned blocks = capped_blocks((long long)n * (c420 ? h / 2 : h) * ((w + 3) / 4));   // units of 4 columns x 2 rows (4:2:0) or x 1 row
-  (deep ? encode_kernel<unsigned short> : encode_kernel<unsigned char>)(chroma, blocks, (hipStream_t)stream_, t, out, n, h, w, matrix,
+  (deep ? encode_kernel<unsigned short> : encode_kernel<unsigned char>)(chroma, layout, blocks, (hipStream_t)stream_, t, out, n, h, w, matrix,
                                                                         full_range, depth);
+  if (layout == FSR_LAYOUT_NV12) {
+    fsr_note_kernel("image_to_nv12_kernel<%s>", deep ? "u16" : "u8");
+    return fsr_check_launch("image_to_nv12_kernel");
+  }
   if (c420) fsr_note_kernel("image_to_i420_kernel<%s>", deep ? "u16" : "u8");
   else fsr_note_kernel("image_to_yuv_kernel<%s,%s>", deep ? "u16" : "u8", chroma == FSR_CHROMA_422 ? "422" : "444");
   return fsr_check_launch(c420 ? "image_to_i420_kernel" : "image_to_yuv_kernel");
@@ -304,6 +335,31 @@ extern "C" int fsr_yuv_to_image(const uint8_t* frames, float* img, int n, int h,
   if (depth > 8 && ((size_t)frames & 1) != 0)
     return fsr_fail(-2, "fsr_yuv_to_image: the payloads of 16-bit samples must be 2-byte aligned");
   return yuv_to_image_launch("fsr_yuv_to_image", frames, img, n, h, w, chroma, siting, matrix, full_range, depth, stream_);
+}
+
+// The payload layout of the _ex entry points: known, and semi-planar with 4:2:0 only
+int fsr_yuv_layout_check(const char* who, int chroma, int layout) {
+  if (layout != FSR_LAYOUT_PLANAR && layout != FSR_LAYOUT_NV12) return fsr_fail(-2, "%s: unknown payload layout %d", who, layout);
+  if (layout == FSR_LAYOUT_NV12 && chroma != FSR_CHROMA_420)
+    return fsr_fail(-2, "%s: the semi-planar layout (NV12, P010 ...) is for 4:2:0 chroma only (chroma %d)", who, chroma);
+  return 0;
+}
+
+extern "C" int fsr_yuv_to_image_ex(const uint8_t* frames, float* img, int n, int h, int w, int chroma, int layout, int siting, int matrix,
+                                   int full_range, int depth, fsr_stream_t stream_) {
+  if (!known_chroma(chroma)) return fsr_fail(-2, "fsr_yuv_to_image_ex: unknown chroma subsampling %d", chroma);
+  if (int rc = fsr_yuv_layout_check("fsr_yuv_to_image_ex", chroma, layout)) return rc;
+  if (depth < 8 || depth > 16) return fsr_fail(-2, "fsr_yuv_to_image_ex: depth %d is outside 8..16", depth);
+  if (depth > 8 && ((size_t)frames & 1) != 0)
+    return fsr_fail(-2, "fsr_yuv_to_image_ex: the payloads of 16-bit samples must be 2-byte aligned");
+  return yuv_to_image_launch("fsr_yuv_to_image_ex", frames, img, n, h, w, chroma, siting, matrix, full_range, depth, stream_, layout);
+}
+
+extern "C" int fsr_image_to_yuv_ex(const float* t, int n, int h, int w, int chroma, int layout, int matrix, int full_range, int depth,
+                                   void* out, fsr_stream_t stream_) {
+  if (!known_chroma(chroma)) return fsr_fail(-2, "fsr_image_to_yuv_ex: unknown chroma subsampling %d", chroma);
+  if (int rc = fsr_yuv_layout_check("fsr_image_to_yuv_ex", chroma, layout)) return rc;
+  return image_to_yuv_launch("fsr_image_to_yuv_ex", t, n, h, w, chroma, matrix, full_range, depth, out, stream_, layout);
 }
 
 extern "C" int fsr_i420_to_image(const uint8_t* frames, float* img, int n, int h, int w, int siting, int matrix, int full_range,

@@ -16,7 +16,7 @@ import torch
 
 from .config import load_config
 from .model import Generator
-from .ops import check_depth, yuv_frame_bytes
+from .ops import check_depth, layout_code, yuv_frame_bytes
 
 parser = ArgumentParser("Real Time Image Super Resolution")
 parser.add_argument("--image_dir", default=None, required=True, type=str)
@@ -271,15 +271,20 @@ class InferencePipeline:
         return self._run(frames, None, out_size)
 
     def run_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
-                out_full_range=None, out_size=None, depth=8, out_depth=None):
+                out_full_range=None, out_size=None, depth=8, out_depth=None, layout="planar", out_layout=None):
         """frames: iterable of planar YUV payloads of h x w (uint8 arrays or bytes of ops.yuv_frame_bytes(h, w, chroma, depth) each).
         Yields the uint8 payloads of the super-resolved frames, of out_chroma (default: chroma) at out_depth (Generator.forward_yuv with
         these colour parameters), in order, batched and pipelined exactly as `run`.  siting=None: "mpeg2" for 4:2:2, "jpeg" otherwise.
         out_size = (out_h, out_w): payloads of that size.  depth / out_depth (8..16, out_depth defaults to depth): bits per sample in and
         out; payloads deeper than 8 bits are 2 bytes per sample and still travel as uint8 arrays.
         Plan keys: ("i420", h, w, colour parameters), then ("size", out_h, out_w) for a resized output, ("depth", depth, out_depth) for any
-        pair but (8, 8), ("chroma", chroma, out_chroma) for any pair but ("420", "420") and ("bands", band_rows) for a banded plan."""
+        pair but (8, 8), ("chroma", chroma, out_chroma) for any pair but ("420", "420"), ("layout", layout, out_layout) for any pair but
+        ("planar", "planar") and ("bands", band_rows) for a banded plan.
+        layout / out_layout ("planar" or "nv12"; out_layout defaults to layout): semi-planar 4:2:0 payloads in / out."""
         out_chroma = chroma if out_chroma is None else out_chroma
+        out_layout = layout if out_layout is None else out_layout
+        layout_code(layout, chroma)
+        layout_code(out_layout, out_chroma)
         if siting is None:
             siting = "mpeg2" if chroma == "422" else "jpeg"
         colour = dict(siting=siting, matrix=matrix, full_range=bool(full_range), out_matrix=out_matrix or matrix,
@@ -293,12 +298,14 @@ class InferencePipeline:
             key += ("depth", depth, out_depth)
         if (chroma, out_chroma) != ("420", "420"):
             key += ("chroma", chroma, out_chroma)
+        if (layout, out_layout) != ("planar", "planar"):
+            key += ("layout", layout, out_layout)
         batch, rows = self._batch_for(h, w), self._bands_for(h, w)
         if rows is not None:
             key += ("bands", rows)
         fmt = self._Format(key, (yuv_frame_bytes(h, w, chroma, depth),),
                            lambda x: model.forward_yuv(x, h, w, chroma=chroma, out_chroma=out_chroma, out_size=out_size, depth=depth,
-                                                       out_depth=out_depth, bands=rows, **colour),
+                                                       out_depth=out_depth, bands=rows, layout=layout, out_layout=out_layout, **colour),
                            batch)
         return self._run((np.frombuffer(f, dtype=np.uint8) if isinstance(f, (bytes, bytearray, memoryview)) else f
                           for f in frames), fmt)

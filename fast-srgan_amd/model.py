@@ -81,7 +81,7 @@ class Generator(torch.nn.Module):
         self._cfg_up = ops.ConvCfg(cd, act=L.ACT_PRELU, pixel_shuffle=True)
         self._cfg_head = ops.ConvCfg(cd, tanh_head=True)
         self._cfg_head_u8 = ops.ConvCfg(cd, tanh_head=True, u8_head=True)
-        self._cfg_head_i420 = {}      # (matrix code, full range) -> ConvCfg of the I420 head
+        self._cfg_head_i420 = {}      # (matrix code, full range, nv12) -> ConvCfg of the I420 / NV12 head
 
     def _native_size(self, h, w, out_size):
         """True when out_size (None or (out_h, out_w)) is the size the network produces for an h x w input."""
@@ -123,16 +123,17 @@ class Generator(torch.nn.Module):
             per = max(nf * 4 ** (u - 1), 3 * 4 ** u)
         return (2 ** 31 - 1) // (int(h) * int(w) * per)
 
-    def _head_i420(self, matrix, full_range):
-        """ConvCfg of the head whose epilogue stores 8-bit I420 planes in (matrix, full_range), made on first use."""
-        key = (ops.yuv_matrix_code(matrix), int(full_range))
+    def _head_i420(self, matrix, full_range, nv12=False):
+        """ConvCfg of the head whose epilogue stores 8-bit I420 planes (nv12: the NV12 payload) in (matrix, full_range), made on first
+        use."""
+        key = (ops.yuv_matrix_code(matrix), int(full_range), int(bool(nv12)))
         cfg = self._cfg_head_i420.get(key)
         if cfg is None:
             cfg = self._cfg_head_i420[key] = ops.ConvCfg(self.compute, tanh_head=True, i420_head=key)
         return cfg
 
     def forward_yuv(self, frames, h, w, chroma="420", out_chroma=None, siting=None, matrix="bt601", full_range=False, out_matrix=None,
-                    out_full_range=None, out_size=None, depth=8, out_depth=None, bands=None):
+                    out_full_range=None, out_size=None, depth=8, out_depth=None, bands=None, layout="planar", out_layout=None):
         """Video inference on planar YUV frames: (N, bytes) uint8 payloads of h x w (odd sizes legal) in, (N, bytes) uint8 payloads of
         (s h) x (s w) out, s = 2 ** n_upsample.  `chroma` in, `out_chroma` out ("420", "422" or "444", independent of each other;
         out_chroma defaults to chroma): payloads are ops.yuv_frame_bytes(h, w, chroma, depth) bytes in and
@@ -147,25 +148,32 @@ class Generator(torch.nn.Module):
         Routes: 8-bit "420" output at the native size (out_size None or that size) is the head's own I420 epilogue.  Anything else is the
         float head followed by ops.image_to_yuv at the native size, or by one fused kernel that resizes (antialiased bicubic) and encodes
         (ops.resample_image) -- "444" on a 4:2:0 source keeps the chroma the head has computed.
-        bands = R: the tail in row bands of R core rows, as forward_u8's; the encode / resize kernels run on the whole frame after it."""
+        bands = R: the tail in row bands of R core rows, as forward_u8's; the encode / resize kernels run on the whole frame after it.
+        layout / out_layout ("planar" or "nv12", independent of each other; out_layout defaults to layout): "nv12" is the semi-planar
+        payload of 4:2:0 frames -- Y, then one plane of (Cb, Cr) pairs; NV12 at depth 8, P010 / P012 / P016 above.  The
+        routes are the same: the head's epilogue stores the NV12 payload itself (FSR_OUT_NV12), the encode and resize kernels have
+        their semi-planar forms."""
         ops.chroma_code(chroma)
         out_chroma = chroma if out_chroma is None else out_chroma
         ops.chroma_code(out_chroma)
+        out_layout = layout if out_layout is None else out_layout
+        ops.layout_code(layout, chroma)
+        ops.layout_code(out_layout, out_chroma)
         depth = ops.check_depth(depth)
         out_depth = depth if out_depth is None else ops.check_depth(out_depth)
         out_matrix = out_matrix or matrix
         out_full = bool(full_range if out_full_range is None else out_full_range)
         native = self._native_size(h, w, out_size)
         epilogue = out_chroma == "420" and native and out_depth == 8
-        cfg = self._head_i420(out_matrix, out_full) if epilogue else self._cfg_head
+        cfg = self._head_i420(out_matrix, out_full, out_layout == "nv12") if epilogue else self._cfg_head
         with torch.no_grad():
-            y = self._forward(ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth), cfg, bands)
+            y = self._forward(ops.yuv_to_image(frames, h, w, chroma, siting, matrix, full_range, depth, layout), cfg, bands)
             if epilogue:
                 return y
             t = y.permute(0, 2, 3, 1)
             if native:
-                return ops.image_to_yuv(t, out_chroma, out_matrix, out_full, out_depth)
-            return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth, out_chroma)
+                return ops.image_to_yuv(t, out_chroma, out_matrix, out_full, out_depth, out_layout)
+            return ops.resample_image(t, int(out_size[0]), int(out_size[1]), "i420", out_matrix, out_full, out_depth, out_chroma, out_layout)
 
     def forward_yuv420(self, frames, h, w, siting="jpeg", matrix="bt601", full_range=False, out_matrix=None, out_full_range=None,
                        out_size=None, depth=8, out_depth=None, bands=None):
@@ -214,6 +222,8 @@ class Generator(torch.nn.Module):
             out = torch.empty((n, oh * ow * 3 // 2), dtype=torch.uint8, device=m.device)
             # (row bytes, output rows per row of m, plane offset in a window's payload, plane offset in a frame's)
             planes = [(ow, 2, 0, 0), (W2, 1, 4 * Hw * W2, oh * ow), (W2, 1, 5 * Hw * W2, oh * ow + H2 * W2)]
+            if cfg_head.i420_head[2]:       # NV12 (`_head_i420`'s key): one chroma plane of ow bytes per row (Cb, Cr pairs)
+                planes = [(ow, 2, 0, 0), (ow, 1, 4 * Hw * W2, oh * ow)]
             src_pitch, dst_pitch = 6 * Hw * W2, oh * ow * 3 // 2
         else:                       # (N, 4H, 4W, 3) uint8 or float32
             out = torch.empty((n, oh, ow, 3), dtype=torch.uint8 if cfg_head.u8_head else torch.float32, device=m.device)

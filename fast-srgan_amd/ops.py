@@ -467,7 +467,8 @@ def conv3x3_raw(cd, x, wpk, cout, *, mode=L.CONV_FWD, out_hw=None, stride=1, bia
     """One fsr_conv3x3 launch.  x: (N,IH,IW,Cin) [or its depth-to-space form when in_pixel_shuffled].
     out_u8 (tanh heads): the output is the finished uint8 HWC image of inference.py:53-56.
     out_i420 = (matrix, full_range) (3-channel tanh heads, even output extents): the output is (N, OH*OW*3/2) uint8, the I420
-    planes of the RGB frame per image (FSR_OUT_I420).
+    planes of the RGB frame per image (FSR_OUT_I420).  A third element that is true -- (matrix, full_range, 1) --
+    asks for the semi-planar payload instead (FSR_OUT_NV12): the same bytes, Cb and Cr interleaved in one plane.
     pool2 (no-grad passes): the output is MaxPool2d(2,2) of the activated result; the full-resolution tensor is never written.
     dact_add: `dact_mask` is ADDED to the result (the gradient of a skip connection) instead of gating it.
     dact_bits: `dact_mask` is the packed sign-bit tensor (N,OH,OW,Cout/8) uint8 of the producing layer's output (stride-2 data gradients)."""
@@ -490,7 +491,7 @@ def conv3x3_raw(cd, x, wpk, cout, *, mode=L.CONV_FWD, out_hw=None, stride=1, bia
     out = _empty(oshape, odt, x.device)
     pre = _empty(oshape, odt, x.device) if want_preact else None
     stats = _assigned((n, cout, 2), x.device) if want_stats else None
-    okind = L.OUT_I420 if out_i420 else (L.OUT_U8 if out_u8 else int(out_f32))
+    okind = (L.OUT_NV12 if len(out_i420) > 2 and out_i420[2] else L.OUT_I420) if out_i420 else (L.OUT_U8 if out_u8 else int(out_f32))
     yuv = out_i420 or (0, 0)
     d = L.ConvDesc(cd.code, mode, n, ih, iw, cin, oh, ow, cout, stride, act, float(slope), int(pixel_shuffle),
                    int(in_pixel_shuffled), okind, int(pool2), 2 if dact_bits else int(bool(dact_add)), 0, int(yuv[0]), int(yuv[1]))
@@ -585,7 +586,8 @@ class ConvCfg:
                  in_scale=(1.0, 1.0, 1.0), in_shift=(0.0, 0.0, 0.0), tanh_head=False, input_act_bwd=None,
                  act_bwd_by_consumer=False, u8_head=False, pool_after=False, n_alias=0, emit_signs=False, i420_head=None):
         # u8_head (inference only, with tanh_head): the head stores the finished uint8 HWC frame instead of float
-        # i420_head = (matrix, full_range) (inference only, with tanh_head): the head stores the I420 planes of the frame
+        # i420_head = (matrix, full_range) (inference only, with tanh_head): the head stores the I420 planes of the frame;
+        # (matrix, full_range, 1): the NV12 payload (one interleaved chroma plane)
         # input_act_bwd = slope: the data-gradient launch also applies the backward of the ReLU (0.0) / LeakyReLU
         #   that produced this conv's input (the mask is the saved input itself), so the tensor it returns is
         #   already the producer's pre-activation gradient;
@@ -1185,6 +1187,19 @@ def chroma_code(chroma):
     return CHROMAS[chroma]
 
 
+YUV_LAYOUTS = {"planar": L.LAYOUT_PLANAR, "nv12": L.LAYOUT_NV12}
+
+
+def layout_code(layout, chroma="420"):
+    """The payload layout's code.  "nv12" (semi-planar: Y, then one plane of (Cb, Cr) pairs; above 8 bits the code sits in the HIGH
+    bits of its 16-bit word -- NV12, P010, P012, P016) exists for chroma "420" only."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError("payload layout must be one of %s, got %r" % (sorted(YUV_LAYOUTS), layout))
+    if layout == "nv12" and chroma != "420":
+        raise ValueError("layout \"nv12\" (semi-planar) is for chroma \"420\" only, got chroma %r" % (chroma,))
+    return YUV_LAYOUTS[layout]
+
+
 def _check_yuv_extents(chroma, h, w):
     """The output extents a subsampling can hold: even ones for "420", an even width for "422", any for "444"."""
     if chroma == "420" and (h % 2 or w % 2):
@@ -1193,22 +1208,27 @@ def _check_yuv_extents(chroma, h, w):
         raise ValueError("4:2:2 output needs an even output width, got %d" % w)
 
 
-def yuv_frame_bytes(h, w, chroma="420", depth=8):
+def yuv_frame_bytes(h, w, chroma="420", depth=8, layout="planar"):
     """Bytes of one planar YUV payload at h x w: the Y plane, then Cb and Cr of ceil(h/2) x ceil(w/2) ("420"), h x ceil(w/2) ("422")
     or h x w ("444") each -- one byte per sample at depth 8, two (little-endian, the value in the low `depth` bits: Y4M's C420p<depth>
-    and its kin) at depths 9..16."""
+    and its kin) at depths 9..16.  layout "nv12" ("420" only): the same samples with Cb and Cr interleaved in one plane, so the same
+    count."""
     chroma_code(chroma)
+    layout_code(layout, chroma)
     ch, cw = (h + 1) // 2 if chroma == "420" else h, w if chroma == "444" else (w + 1) // 2
     return (h * w + 2 * ch * cw) * (2 if check_depth(depth) > 8 else 1)
 
 
-def yuv_to_image(frames, h, w, chroma="420", siting=None, matrix="bt601", full_range=False, depth=8):
+def yuv_to_image(frames, h, w, chroma="420", siting=None, matrix="bt601", full_range=False, depth=8, layout="planar"):
     """(N, yuv_frame_bytes(h, w, chroma, depth)) uint8 planar YUV payloads -> float32 (N,3,H,W) VIEW in [-1,1] of an NHWC buffer (2 c - 1
     of the decoded RGB; fsr_yuv_to_image), the layout u8_to_image returns.  depth 9..16: payloads of 16-bit samples,
     still a uint8 tensor.  "420": chroma upsampled bilinearly at `siting` "jpeg" (centred, the default) or "mpeg2" (co-sited
     horizontally).  "422": chroma interpolated horizontally only, linearly with edge clamp, at "mpeg2" (co-sited with the even luma
-    columns: what Y4M's C422 means, and the default) or "jpeg".  "444": no interpolation, `siting` is ignored."""
+    columns: what Y4M's C422 means, and the default) or "jpeg".  "444": no interpolation, `siting` is ignored.
+    layout "nv12" ("420" only; fsr_yuv_to_image_ex): semi-planar payloads -- NV12 at depth 8, P010 / P012 / P016 above,
+    whose low 16 - depth bits are ignored."""
     code = chroma_code(chroma)
+    lcode = layout_code(layout, chroma)
     _check_dev(frames)
     depth = check_depth(depth)
     if siting is None or chroma == "444":
@@ -1225,19 +1245,26 @@ def yuv_to_image(frames, h, w, chroma="420", siting=None, matrix="bt601", full_r
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    L.check(L.lib().fsr_yuv_to_image(_p(frames), _p(img), n, h, w, code, CHROMA_SITINGS[siting], yuv_matrix_code(matrix),
-                                     int(bool(full_range)), depth, _stream()), "fsr_yuv_to_image")
+    if lcode != L.LAYOUT_PLANAR:
+        L.check(L.lib().fsr_yuv_to_image_ex(_p(frames), _p(img), n, h, w, code, lcode, CHROMA_SITINGS[siting], yuv_matrix_code(matrix),
+                                            int(bool(full_range)), depth, _stream()), "fsr_yuv_to_image_ex")
+    else:
+        L.check(L.lib().fsr_yuv_to_image(_p(frames), _p(img), n, h, w, code, CHROMA_SITINGS[siting], yuv_matrix_code(matrix),
+                                         int(bool(full_range)), depth, _stream()), "fsr_yuv_to_image")
     if prof is not None:
         ev1.record()
         prof.append(("decode", chroma, ev0, ev1, img.numel() * 4 + frames.numel()))
     return img.permute(0, 3, 1, 2)
 
 
-def image_to_yuv(t_nhwc, chroma="420", matrix="bt601", full_range=False, depth=8):
+def image_to_yuv(t_nhwc, chroma="420", matrix="bt601", full_range=False, depth=8, layout="planar"):
     """The planar YUV encode of DESIGN.md §6c on its own (fsr_image_to_yuv): contiguous float32 (N,H,W,3) tanh output -> uint8
     (N, yuv_frame_bytes(H, W, chroma, depth)) payloads, depth 8..16 -- for "420" what the head's FSR_OUT_I420 epilogue computes, at any
-    depth.  "420" needs even H and W; "422" an even W (chroma co-sited with the even luma columns); "444" takes any extents."""
+    depth.  "420" needs even H and W; "422" an even W (chroma co-sited with the even luma columns); "444" takes any extents.
+    layout "nv12" ("420" only; fsr_image_to_yuv_ex): the same codes as a semi-planar payload -- NV12 at depth 8, P010 /
+    P012 / P016 above (the code in the high bits, the low 16 - depth bits zero)."""
     code = chroma_code(chroma)
+    lcode = layout_code(layout, chroma)
     _check_dev(t_nhwc)
     depth = check_depth(depth)
     if t_nhwc.dtype != torch.float32 or t_nhwc.dim() != 4 or t_nhwc.shape[3] != 3 or not t_nhwc.is_contiguous():
@@ -1249,8 +1276,12 @@ def image_to_yuv(t_nhwc, chroma="420", matrix="bt601", full_range=False, depth=8
     if prof is not None:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
-    L.check(L.lib().fsr_image_to_yuv(_p(t_nhwc), n, h, w, code, yuv_matrix_code(matrix), int(bool(full_range)), depth, _p(out), _stream()),
-            "fsr_image_to_yuv")
+    if lcode != L.LAYOUT_PLANAR:
+        L.check(L.lib().fsr_image_to_yuv_ex(_p(t_nhwc), n, h, w, code, lcode, yuv_matrix_code(matrix), int(bool(full_range)), depth, _p(out),
+                                            _stream()), "fsr_image_to_yuv_ex")
+    else:
+        L.check(L.lib().fsr_image_to_yuv(_p(t_nhwc), n, h, w, code, yuv_matrix_code(matrix), int(bool(full_range)), depth, _p(out), _stream()),
+                "fsr_image_to_yuv")
     if prof is not None:
         ev1.record()
         prof.append(("encode", chroma, ev0, ev1, t_nhwc.numel() * 4 + out.numel()))
@@ -1294,7 +1325,7 @@ def aa_taps(in_size, out_size, device):
     return hit
 
 
-def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=False, depth=8, chroma="420"):
+def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=False, depth=8, chroma="420", layout="planar"):
     """Antialiased bicubic resize of a head output to out_h x out_w, fused with the output conversion (fsr_resample_image;
     DESIGN.md §6d).  t_nhwc: contiguous float32 (N,H,W,3) tanh output (the NHWC buffer behind Generator.forward's view).
       kind "f32" : float32 (N,3,out_h,out_w) VIEW of an NHWC buffer, 2 v - 1 of the resized c = (t + 1) / 2 -- what
@@ -1302,10 +1333,14 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
       kind "u8"  : uint8 (N,out_h,out_w,3), (unsigned char)(clamp(v, 0, 1) * 255): forward_u8's bytes at another size;
       kind "i420": uint8 (N, yuv_frame_bytes(out_h, out_w, chroma, depth)), the planes of image_to_yuv for clamp(v, 0, 1) in (matrix,
                    full_range) (fsr_resample_image_yuv): "420" needs even extents, "422" an even out_w, "444" takes any; depth 9..16:
-                   16-bit samples.  The other kinds take chroma "420" and depth 8 only."""
+                   16-bit samples.  layout "nv12" (chroma "420" only): image_to_yuv's semi-planar payload (fsr_resample_image_yuv_ex).
+                   The other kinds take chroma "420", depth 8 and layout "planar" only."""
     _check_dev(t_nhwc)
     depth = check_depth(depth)
     ccode = chroma_code(chroma)
+    lcode = layout_code(layout, chroma)
+    if layout != "planar" and kind != "i420":
+        raise ValueError("resample_image: layout %r is for kind \"i420\" only, got kind %r" % (layout, kind))
     if chroma != "420" and kind != "i420":
         raise ValueError("resample_image: chroma %r is for kind \"i420\" only" % (chroma,))
     if depth != 8 and kind != "i420":
@@ -1334,7 +1369,10 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
     taps = (_p(wy), _p(ymin), _p(ysize), ky, _p(wx), _p(xmin), _p(xsize), kx)
-    if kind == "i420":
+    if kind == "i420" and lcode != L.LAYOUT_PLANAR:
+        L.check(L.lib().fsr_resample_image_yuv_ex(_p(t_nhwc), n, h, w, out_h, out_w, *taps, ccode, lcode, mcode, int(bool(full_range)), depth,
+                                                  _p(out), _stream()), "fsr_resample_image_yuv_ex")
+    elif kind == "i420":
         L.check(L.lib().fsr_resample_image_yuv(_p(t_nhwc), n, h, w, out_h, out_w, *taps, ccode, mcode, int(bool(full_range)), depth, _p(out),
                                                _stream()), "fsr_resample_image_yuv")
     else:

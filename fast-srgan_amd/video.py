@@ -26,6 +26,18 @@ Frames above 1080p (2560x1440, up to 3840x2160) run with the generator's tail in
 the same bytes a whole frame would give, `--band_rows` rows of the last up-sampling stage at a time.  `--bands on` bands smaller frames
 too, for a larger batch; `--bands off` refuses what does not fit whole.
 
+Raw streams (`--in_format` / `--out_format`: `yuv420p`, `nv12`, `p010`, `p012`, `p016`; the default is `y4m`) carry no header: what
+`ffmpeg -f rawvideo -pix_fmt nv12` writes, and what a hardware decoder hands over (`ffmpeg -hwaccel vaapi ... -pix_fmt nv12` or `p010le`).
+A raw input needs `--in_size WxH`; `--fps N[:D]` (default 25:1) is only used for the Y4M header when raw goes to Y4M.  `yuv420p` is 8-bit
+planar 4:2:0; `nv12` is the semi-planar 8-bit frame -- Y, then one plane of (Cb, Cr) pairs --, and `p010` / `p012` / `p016` its 16-bit
+forms with the code in the HIGH bits of each little-endian word.  The device reads and writes these layouts itself: no
+de-interleaving pass on the host.  `--out_format` defaults to the input's kind: `y4m` for a Y4M input, for a raw input the raw format of
+the same family at the output depth.  A `p01x` name fixes the depth, so an `--out_depth` that contradicts `--out_format` is an error.
+For a raw output the status line prints the ffmpeg arguments that read it.
+
+    ffmpeg -hwaccel vaapi -i in.mp4 -vf hwdownload,format=nv12 -f rawvideo -pix_fmt nv12 - | \
+        python video.py --input - --in_format nv12 --in_size 1920x1080 --fps 30000:1001 --output - | ffmpeg -f rawvideo ...
+
 Like inference.py, the CLI loads configs/config.yaml and models/model.pt from the working directory.  `-` is stdin /
 stdout; with `--output -` nothing but the stream goes to stdout (status lines go to stderr).  Frames are read lazily, one
 device batch at a time: a stream of any length passes through a pipe.
@@ -41,6 +53,10 @@ from .ops import check_depth, i420_frame_bytes, yuv_frame_bytes
 MATRICES = ("bt601", "bt709")
 SITINGS = ("jpeg", "mpeg2")
 CHROMAS = ("420", "422", "444")
+# stream formats: name -> (layout, depth, ffmpeg's -pix_fmt); "y4m" is the container, the others are headerless 4:2:0 frames
+RAW_FORMATS = {"yuv420p": ("planar", 8, "yuv420p"), "nv12": ("nv12", 8, "nv12"), "p010": ("nv12", 10, "p010le"),
+               "p012": ("nv12", 12, "p012le"), "p016": ("nv12", 16, "p016le")}
+FORMATS = ("y4m",) + tuple(RAW_FORMATS)
 
 
 class Y4MError(ValueError):
@@ -193,9 +209,103 @@ class Y4MWriter:
         self.f.write(payload)
 
 
+class RawReader:
+    """Headerless frames of `frame_bytes` bytes each (the caller knows the format: --in_format / --in_size): `frames()` yields one uint8
+    payload per frame, reading only that frame from the file.  A truncated last frame is an error, as in Y4MReader."""
+
+    def __init__(self, f, width, height, frame_bytes):
+        if width <= 0 or height <= 0 or frame_bytes <= 0:
+            raise ValueError("RawReader: bad frame size %dx%d (%d bytes)" % (width, height, frame_bytes))
+        self.f, self.width, self.height, self.frame_bytes = f, int(width), int(height), int(frame_bytes)
+
+    def frames(self):
+        idx = 0
+        while True:
+            buf = bytearray(self.frame_bytes)
+            view, got = memoryview(buf), 0
+            while got < self.frame_bytes:
+                k = self.f.readinto(view[got:])
+                if not k:
+                    if got == 0:
+                        return
+                    raise Y4MError("raw stream: frame %d is truncated (%d of %d bytes)" % (idx, got, self.frame_bytes))
+                got += k
+            yield np.frombuffer(buf, dtype=np.uint8)
+            idx += 1
+
+
+class RawWriter:
+    """One payload of `frame_bytes` bytes per frame, nothing else."""
+
+    def __init__(self, f, width, height, frame_bytes):
+        self.f, self.width, self.height, self.frame_bytes = f, int(width), int(height), int(frame_bytes)
+
+    def write_frame(self, payload):
+        payload = memoryview(np.ascontiguousarray(payload)).cast("B")
+        if payload.nbytes != self.frame_bytes:
+            raise Y4MError("raw stream: a frame of %d bytes does not match the stream's %d" % (payload.nbytes, self.frame_bytes))
+        self.f.write(payload)
+
+
+def resolve_formats(in_format, out_format, out_depth, out_chroma, in_depth=None):
+    """The (out_format, out_depth) of a run, or ValueError.  in_depth: the input's depth (None before a Y4M stream is opened: then only
+    what the flags alone decide is checked).  out_format defaults to the input's kind: "y4m" for Y4M, for a raw input the raw format of
+    its family (planar / semi-planar) at the output depth.  A raw name fixes chroma 4:2:0 and its depth."""
+    if in_format != "y4m":
+        in_depth = RAW_FORMATS[in_format][1]
+    depth = out_depth if out_depth is not None else (RAW_FORMATS[out_format][1] if out_format in RAW_FORMATS else in_depth)
+    if out_format is None:
+        if in_format == "y4m":
+            out_format = "y4m"
+        elif depth is not None:
+            if RAW_FORMATS[in_format][0] == "planar":
+                if depth != 8:
+                    raise ValueError("--out_depth %d: raw planar output is yuv420p, 8 bits; pick --out_format y4m or p0%d" % (depth, depth))
+                out_format = "yuv420p"
+            else:
+                out_format = {8: "nv12", 10: "p010", 12: "p012", 16: "p016"}.get(depth)
+                if out_format is None:
+                    raise ValueError("--out_depth %d has no raw semi-planar format (nv12, p010, p012, p016)" % depth)
+    if out_format in RAW_FORMATS:
+        if depth is not None and depth != RAW_FORMATS[out_format][1]:
+            raise ValueError("--out_depth %d contradicts --out_format %s, which is %d bits per sample"
+                             % (depth, out_format, RAW_FORMATS[out_format][1]))
+        if out_chroma not in (None, "420"):
+            raise ValueError("--out_format %s is a 4:2:0 format: --out_chroma %s needs --out_format y4m" % (out_format, out_chroma))
+    return out_format, depth
+
+
+def parse_size(text, flag):
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+        if w <= 0 or h <= 0:
+            raise ValueError
+    except ValueError:
+        raise ValueError("%s must be WxH of positive integers, got %r" % (flag, text))
+    return w, h
+
+
+def parse_fps(text):
+    n, _, d = text.partition(":")
+    try:
+        n, d = int(n), int(d or 1)
+        if n <= 0 or d <= 0:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--fps must be N or N:D of positive integers, got %r" % text)
+    return "%d:%d" % (n, d)
+
+
 parser = ArgumentParser("Real Time Video Super Resolution (Y4M, planar YUV)")
-parser.add_argument("--input", required=True, type=str, help="Y4M stream, or - for stdin")
-parser.add_argument("--output", required=True, type=str, help="Y4M stream, or - for stdout")
+parser.add_argument("--input", required=True, type=str, help="Y4M (or raw, --in_format) stream, or - for stdin")
+parser.add_argument("--output", required=True, type=str, help="Y4M (or raw, --out_format) stream, or - for stdout")
+parser.add_argument("--in_format", default="y4m", choices=FORMATS,
+                    help="y4m, or headerless 4:2:0 frames: yuv420p (8-bit planar), nv12 (8-bit semi-planar), p010 / p012 / p016 (16-bit "
+                         "semi-planar, the code in the high bits); raw formats need --in_size")
+parser.add_argument("--out_format", default=None, choices=FORMATS,
+                    help="format of the output (default: the input's kind -- y4m for Y4M, the raw format of the same family at the output depth)")
+parser.add_argument("--in_size", default=None, type=str, metavar="WxH", help="frame size of a raw input")
+parser.add_argument("--fps", default=None, type=str, metavar="N[:D]", help="frame rate of a raw input, for the Y4M header (default 25:1)")
 parser.add_argument("--compute_dtype", default=None, choices=["bf16", "f16", "x3", "x3v", "f32"], help="kernel precision")
 parser.add_argument("--batch", default=8, type=int, help="frames per device batch")
 parser.add_argument("--matrix", default="bt601", choices=MATRICES, help="colour matrix of the input")
@@ -245,15 +355,37 @@ def main(argv=None):
         video_out_size(2, 2, args.size, args.scale, args.out_chroma or "420")
     except ValueError as exc:
         raise SystemExit("video: %s%s" % (exc, "" if args.out_chroma else " (an odd --size needs --out_chroma 422 or 444 spelled out)"))
+    try:    # so do the format flags, as far as they can be judged without the stream
+        raw_in = args.in_format != "y4m"
+        if raw_in and args.in_size is None:
+            raise ValueError("--in_format %s is a headerless stream: it needs --in_size WxH" % args.in_format)
+        if not raw_in and args.in_size is not None:
+            raise ValueError("--in_size is for raw input formats; a Y4M stream declares its size")
+        in_size = parse_size(args.in_size, "--in_size") if raw_in else None
+        fps = parse_fps(args.fps) if args.fps is not None else None
+        resolve_formats(args.in_format, args.out_format, args.out_depth, args.out_chroma)
+    except ValueError as exc:
+        raise SystemExit("video: %s" % exc)
     if not torch.cuda.is_available():
         raise SystemExit("fast-srgan_amd runs on an MI355X only: no GPU is visible")
     fin = sys.stdin.buffer if args.input == "-" else open(args.input, "rb")
     fout = sys.stdout.buffer if args.output == "-" else open(args.output, "wb")
     try:
-        reader = Y4MReader(fin, max_depth=16, chroma=CHROMAS)
+        if raw_in:
+            layout, in_depth, _ = RAW_FORMATS[args.in_format]
+            reader = RawReader(fin, in_size[0], in_size[1], yuv_frame_bytes(in_size[1], in_size[0], "420", in_depth, layout))
+            reader.depth, reader.chroma, reader.siting, reader.colour_range = in_depth, "420", "jpeg", None
+            reader.frame_rate, reader.aspect, reader.interlace = fps or "25:1", None, None
+        else:
+            layout = "planar"
+            reader = Y4MReader(fin, max_depth=16, chroma=CHROMAS)
         siting = args.siting or reader.siting
         chroma, out_chroma = reader.chroma, args.out_chroma or reader.chroma
-        out_depth = reader.depth if args.out_depth is None else args.out_depth
+        try:
+            out_format, out_depth = resolve_formats(args.in_format, args.out_format, args.out_depth, out_chroma, reader.depth)
+        except ValueError as exc:
+            raise SystemExit("video: %s" % exc)
+        out_layout = RAW_FORMATS[out_format][0] if out_format in RAW_FORMATS else "planar"
         full = (reader.colour_range or args.range) == "full"
         out_full = full if args.out_range is None else args.out_range == "full"
         out_matrix = args.out_matrix or args.matrix
@@ -269,7 +401,11 @@ def main(argv=None):
         _status("video: %dx%d -> %dx%d%s, %s %s %d-bit -> %s %s %d-bit, chroma siting %s%s" % (
             w, h, ow, oh, "" if out_size is None else " (network %dx%d, resized)" % (s * w, s * h),
             args.matrix, "full" if full else "limited", reader.depth, out_matrix, "full" if out_full else "limited", out_depth, siting,
-            ", 4:%s:%s -> 4:%s:%s" % (chroma[1], chroma[2], out_chroma[1], out_chroma[2])))
+            ", 4:%s:%s -> 4:%s:%s" % (chroma[1], chroma[2], out_chroma[1], out_chroma[2])
+            + ("" if (args.in_format, out_format) == ("y4m", "y4m") else ", %s -> %s" % (args.in_format, out_format))))
+        if out_format in RAW_FORMATS:
+            rate = (fps or reader.frame_rate or "25:1").replace(":", "/")
+            _status("video: read the output with: -f rawvideo -pix_fmt %s -s %dx%d -r %s" % (RAW_FORMATS[out_format][2], ow, oh, rate))
         try:
             pipe = InferencePipeline(model, "cuda", batch=args.batch, copy=False, bands=args.bands, band_rows=args.band_rows)
         except ValueError as exc:
@@ -277,11 +413,14 @@ def main(argv=None):
         try:
             frames_out = pipe.run_yuv(reader.frames(), h, w, chroma=chroma, out_chroma=out_chroma, siting=siting, matrix=args.matrix,
                                       full_range=full, out_matrix=out_matrix, out_full_range=out_full, out_size=out_size,
-                                      depth=reader.depth, out_depth=out_depth)
+                                      depth=reader.depth, out_depth=out_depth, layout=layout, out_layout=out_layout)
         except ValueError as exc:       # a frame too large for the kernels: refused before anything is allocated or written
             raise SystemExit("video: %s" % exc)
         batch = pipe._batch_for(h, w)       # (the pipeline has reported a batch it had to reduce, or a shape it runs in row bands)
-        writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth, chroma=out_chroma)
+        if out_format in RAW_FORMATS:
+            writer = RawWriter(fout, ow, oh, yuv_frame_bytes(oh, ow, "420", out_depth, out_layout))
+        else:
+            writer = Y4MWriter(fout, ow, oh, reader.frame_rate, reader.aspect, reader.interlace, out_full, depth=out_depth, chroma=out_chroma)
         n, t0, t1 = 0, time.perf_counter(), None
         for y in frames_out:
             writer.write_frame(y)       # (a view of the pinned result buffer: written before the slot is reused)

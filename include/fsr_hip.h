@@ -46,16 +46,17 @@
 extern "C" {
 #endif
 
-#define FSR_ABI_VERSION 15
+#define FSR_ABI_VERSION 16
 
 enum { FSR_F32 = 0, FSR_BF16 = 1, FSR_F16 = 2, FSR_X3 = 3 };
 enum { FSR_ACT_NONE = 0, FSR_ACT_RELU = 1, FSR_ACT_LEAKY = 2, FSR_ACT_PRELU = 3, FSR_ACT_TANH = 4 };
 enum { FSR_CONV_FWD = 0, FSR_CONV_DGRAD = 1 };
 enum { FSR_PACK_FWD = 0, FSR_PACK_FWD_PS = 1, FSR_PACK_DGRAD = 2, FSR_PACK_DGRAD_PS = 3 };
-enum { FSR_OUT_DTYPE = 0, FSR_OUT_F32 = 1, FSR_OUT_U8 = 2, FSR_OUT_I420 = 3 };   /* fsr_conv_desc.out_f32 */
+enum { FSR_OUT_DTYPE = 0, FSR_OUT_F32 = 1, FSR_OUT_U8 = 2, FSR_OUT_I420 = 3, FSR_OUT_NV12 = 4 };   /* fsr_conv_desc.out_f32 */
 enum { FSR_YUV_BT601 = 0, FSR_YUV_BT709 = 1 };             /* fsr_conv_desc.yuv_matrix, fsr_i420_to_image */
 enum { FSR_SITING_JPEG = 0, FSR_SITING_MPEG2 = 1 };        /* chroma siting of fsr_i420_to_image's input */
 enum { FSR_CHROMA_420 = 0, FSR_CHROMA_422 = 1, FSR_CHROMA_444 = 2 };   /* chroma subsampling of the fsr_*_yuv entry points */
+enum { FSR_LAYOUT_PLANAR = 0, FSR_LAYOUT_NV12 = 1 };       /* payload layout of the fsr_*_yuv_ex entry points */
 
 typedef void* fsr_stream_t; /* hipStream_t */
 
@@ -107,7 +108,8 @@ int fsr_pack_conv3x3_lin(int dtype, int mode, const float* w_oihw, int cout, int
  *   out [n,oh,ow,cout] bytes (cout = 3: the finished RGB frame); FSR_OUT_I420 (3, FSR_ACT_TANH heads, forward, stride 1,
  *   cout = 3, even oh and ow, no statistics / pre-activation / mask / scale tensors): store the I420 (planar YUV 4:2:0) frame of the
  *   RGB head output -- per image the Y plane [oh][ow], then Cb and Cr [oh/2][ow/2] (oh * ow * 3 / 2 bytes, C420jpeg siting:
- *   chroma is the mean of the 2x2 block), matrix and range from yuv_matrix / yuv_full_range.
+ *   chroma is the mean of the 2x2 block), matrix and range from yuv_matrix / yuv_full_range; FSR_OUT_NV12 (4, ABI 16; the
+ *   conditions of FSR_OUT_I420): the same codes as the NV12 frame -- the Y plane, then ONE plane [oh/2][ow/2] of (Cb, Cr) byte pairs.
  * pool2 (inference / no-grad passes of vgg19.features, model.py:8,191): the kernel's epilogue takes the 2x2 maximum of the
  *   activated outputs and stores only the pooled tensor -- the full-resolution tensor, which only a backward pass would
  *   read, is never written.  oh, ow even; cout %% 16 == 0; no stats / preact / mask tensors.
@@ -140,8 +142,8 @@ typedef struct fsr_conv_desc {
                          gradients, 16-bit dtypes and FSR_X3): it is the PACKED SIGN-BIT tensor [n][oh][ow][cout / 8] of the producing layer's output
                          (bit c & 7 of byte c >> 3 = output > 0: fsr_conv3x3_c3_fwd's `signs`), gating like 0 at a sixteenth of the bytes */
   int pack_lin; /* 0: packed_w is fsr_pack_conv3x3's layout; 64 / 128: fsr_pack_conv3x3_lin's with that block (must equal fsr_conv3x3_pack_block) */
-  int yuv_matrix;     /* FSR_OUT_I420: FSR_YUV_BT601 or FSR_YUV_BT709 (ignored by the other output kinds) */
-  int yuv_full_range; /* FSR_OUT_I420: 0 limited range (Y 16..235, C 16..240), 1 full range (0..255) */
+  int yuv_matrix;     /* FSR_OUT_I420 / FSR_OUT_NV12: FSR_YUV_BT601 or FSR_YUV_BT709 (ignored by the other output kinds) */
+  int yuv_full_range; /* FSR_OUT_I420 / FSR_OUT_NV12: 0 limited range (Y 16..235, C 16..240), 1 full range (0..255) */
 } fsr_conv_desc;
 
 /* Block size of the stage-contiguous filter pack (fsr_pack_conv3x3_lin) that the kernel fsr_conv3x3 would dispatch for `desc`
@@ -273,6 +275,18 @@ int fsr_yuv_to_image(const uint8_t* frames, float* img, int n, int h, int w, int
                      fsr_stream_t stream);
 int fsr_image_to_yuv(const float* t, int n, int h, int w, int chroma, int matrix, int full_range, int depth, void* out, fsr_stream_t stream);
 
+/* Semi-planar 4:2:0 (ABI 16): `layout` FSR_LAYOUT_PLANAR is the call above; FSR_LAYOUT_NV12 (FSR_CHROMA_420 only) is the payload
+ * hardware decoders produce -- Y [h][w], then ONE plane of [(h+1)/2] rows of [(w+1)/2] (Cb, Cr) pairs, Cb first; 1 byte per sample at depth 8
+ * (NV12), 2 little-endian bytes at depth 9..16 with the code in the HIGH `depth` bits (P010, P012, P016): written with the low 16 - depth bits
+ * zero, read as stored >> (16 - depth) whatever they hold.  The byte count is the planar payload's, and so is every code: matrices, ranges,
+ * sitings, clamps, rounding and the order of the chroma sum are unchanged, only the addresses and the shift differ.  Refused: an unknown layout,
+ * FSR_LAYOUT_NV12 with another chroma, and whatever the planar calls refuse (odd encode extents, depth outside 8..16, misaligned 16-bit
+ * payloads).  NV21, NV16 / NV24 and pitched surfaces are not supported. */
+int fsr_yuv_to_image_ex(const uint8_t* frames, float* img, int n, int h, int w, int chroma, int layout, int siting, int matrix, int full_range,
+                        int depth, fsr_stream_t stream);
+int fsr_image_to_yuv_ex(const float* t, int n, int h, int w, int chroma, int layout, int matrix, int full_range, int depth, void* out,
+                        fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ arbitrary output size: antialiased bicubic resize of the head output
  * t: the head's float tanh output [n,h,w,3] (FSR_OUT_F32 of any dtype's head) -> an oh x ow image in ONE fused kernel (horizontal pass
  * of a tile's source-row window into LDS, vertical pass from LDS, conversion, store; no global intermediate, no atomics).  The
@@ -299,6 +313,10 @@ int fsr_resample_image_i420_deep(const float* t, int n, int h, int w, int oh, in
 int fsr_resample_image_yuv(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
                            const float* wx, const int* xmin, const int* xsize, int kx, int chroma, int yuv_matrix, int yuv_full_range,
                            int depth, void* out, fsr_stream_t stream);
+/* ... with the payload `layout` of fsr_image_to_yuv_ex (ABI 16): FSR_LAYOUT_NV12 (FSR_CHROMA_420, oh and ow even) stores the semi-planar frame. */
+int fsr_resample_image_yuv_ex(const float* t, int n, int h, int w, int oh, int ow, const float* wy, const int* ymin, const int* ysize, int ky,
+                              const float* wx, const int* xmin, const int* xsize, int kx, int chroma, int layout, int yuv_matrix,
+                              int yuv_full_range, int depth, void* out, fsr_stream_t stream);
 
 /* ------------------------------------------------------------------ first-layer convolutions straight from the image
  * Conv2d(3 -> cout, k3, p1) of Generator.neck (model.py:75-78), Discriminator.neck (model.py:143-146) and

@@ -35,11 +35,22 @@
        (d) the row-copy kernel alone from its own events (f16, 1080p, R = 128): the gather of the last up-sampling convolution's
            input and the scatter of the uint8 frame, over the bytes moved (read + written).
 
+  7. `--layout`: semi-planar frames (NV12, P010) beside their planar twins, f16, device events, planar and semi-planar
+     interleaved round by round (the order reversed every other round):
+       (a) the decode, encode and resample kernels alone at 1080p output, batch 4, 8 and 10 bits, from their own events
+           (ops.PROFILE_YUV / PROFILE_RESAMPLE; the resample takes 1440x2560 to 1080p, the 9-tap form);
+       (b) model only at 180x320 -> 720x1280, batch 32, one hipGraph each: forward_yuv planar in and out (the head's I420 epilogue),
+           planar in / NV12 out (the head's NV12 epilogue) and NV12 in and out.
+     Every semi-planar figure is printed with the spread (max - min over the rounds) its planar twin shows on the same device, and
+     whether it lies within it.  `--planar_only` measures the planar paths alone (the same code on another build of the library: the
+     parent commit's tree, say); `--out FILE` (default profiles/video_bench_nv12.txt) also keeps the lines in a file.
+
     python tools/video_bench.py [--frames 2048] [--rounds 7] [--replays 20] [--modes f16,x3]
     python tools/video_bench.py --resize [--rounds 7] [--replays 20]
     python tools/video_bench.py --deep [--rounds 7] [--replays 20]
     python tools/video_bench.py --chroma [--rounds 7] [--replays 20]
     python tools/video_bench.py --bands [--rounds 7] [--replays 20] [--modes f16,x3]
+    python tools/video_bench.py --layout [--rounds 5] [--replays 20] [--planar_only] [--out FILE]
 """
 import argparse
 import importlib
@@ -394,6 +405,97 @@ def rows_kernel_leg(sd, mode="f16", h=1080, w=1920, R=128):
                                            nbytes / (ms[len(ms) // 2] * 1e-3) / 1e12), flush=True)
 
 
+def layout_leg(sd, rounds, replays, planar_only=False, out=None, mode="f16"):
+    dev = "cuda:0"
+    rounds = max(3, rounds)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    G = pkg.Generator(types.SimpleNamespace(n_filters=64, n_layers=8), compute_dtype=mode)
+    G.load_state_dict(sd)
+    G.to(dev).eval()
+    rng = np.random.default_rng(0)
+    layouts = ("planar",) if planar_only else ("planar", "nv12")
+    say("layout      device %s, %s, %d rounds, planar and semi-planar interleaved; spread = (max - min) / median over the rounds"
+        % (torch.cuda.get_device_name(0), mode, rounds))
+
+    def kw(layout):     # (a build without the keyword measures its planar paths with the same code)
+        return {} if layout == "planar" else {"layout": layout}
+
+    def payload(b, h, w, d):
+        # random bytes are legal in either layout (16-bit semi-planar samples: the low bits are ignored)
+        return torch.from_numpy(rng.integers(0, 256, size=(b, ops.yuv_frame_bytes(h, w, "420", d)), dtype=np.uint8)).to(dev)
+
+    def verdict(name, unit, t):
+        """t: layout -> per-round figures.  Prints each path, and for the semi-planar one where it lies against the planar spread."""
+        mp = statistics.median(t["planar"])
+        sp = max(t["planar"]) - min(t["planar"])
+        say("layout      %-46s planar %9.2f %s  spread %5.2f %%  [per round %s]" % (
+            name, mp, unit, 100.0 * sp / mp, " ".join("%.2f" % v for v in t["planar"])))
+        if "nv12" in t:
+            ms = statistics.median(t["nv12"])
+            where = "within the planar spread" if abs(ms - mp) <= sp else ("outside it: FASTER" if ms < mp else "outside it: SLOWER")
+            say("layout      %-46s nv12   %9.2f %s  %+6.2f %% against planar, %s  [per round %s]" % (
+                name, ms, unit, 100.0 * (ms / mp - 1.0), where, " ".join("%.2f" % v for v in t["nv12"])))
+
+    # (a) the kernels alone, from their own events
+    b, oh, ow = 4, 1080, 1920
+    t_enc = (torch.rand(b, oh, ow, 3, device=dev) * 2.2 - 1.1).contiguous()
+    t_rs = (torch.rand(b, 1440, 2560, 3, device=dev) * 2.2 - 1.1).contiguous()
+    for d in (8, 10):
+        x = payload(b, oh, ow, d)
+        runs = [("decode   %dx%d batch %d, %2d bits" % (ow, oh, b, d), "PROFILE_YUV", lambda lay: ops.yuv_to_image(x, oh, ow, depth=d, **kw(lay))),
+                ("encode   %dx%d batch %d, %2d bits" % (ow, oh, b, d), "PROFILE_YUV", lambda lay: ops.image_to_yuv(t_enc, depth=d, **kw(lay))),
+                ("resample 2560x1440 -> %dx%d batch %d, %2d bits" % (ow, oh, b, d), "PROFILE_RESAMPLE",
+                 lambda lay: ops.resample_image(t_rs, oh, ow, "i420", depth=d, **kw(lay)))]
+        for name, hook, fn in runs:
+            times = {lay: [] for lay in layouts}
+            for lay in layouts:
+                for _ in range(5):
+                    fn(lay)
+            torch.cuda.synchronize()
+            for r in range(rounds):
+                for lay in (layouts if r % 2 == 0 else layouts[::-1]):
+                    setattr(ops, hook, [])
+                    for _ in range(30):
+                        fn(lay)
+                    torch.cuda.synchronize()
+                    prof = getattr(ops, hook)
+                    setattr(ops, hook, None)
+                    us = sorted(1e3 * e[-3].elapsed_time(e[-2]) for e in prof)
+                    times[lay].append(us[len(us) // 2])
+            verdict(name, "us", times)
+        del x
+    del t_enc, t_rs
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    # (b) model only, one graph per path
+    x_p = payload(B, H, W, 8)
+    paths = [("planar", graphed(lambda x: G.forward_yuv(x, H, W), x_p))]
+    if not planar_only:
+        paths += [("nv12 out", graphed(lambda x: G.forward_yuv(x, H, W, out_layout="nv12"), x_p)),
+                  ("nv12 in and out", graphed(lambda x: G.forward_yuv(x, H, W, layout="nv12"), x_p))]
+    times = [[] for _ in paths]
+    for _, g in paths:
+        time_graph(g, 3)
+    for r in range(rounds):
+        order = list(range(len(paths)))
+        for i in (order if r % 2 == 0 else order[::-1]):
+            times[i].append(1e3 * time_graph(paths[i][1], replays))
+    for i in range(1, max(2, len(paths))):
+        t = {"planar": times[0]}
+        if i < len(paths):
+            t["nv12"] = times[i]
+        verdict("model %dx%d -> %dx%d batch %d%s" % (W, H, 4 * W, 4 * H, B, ", " + paths[i][0] if i < len(paths) else ""), "ms", t)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def end_to_end(sd, frames, mode):
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "configs"))
@@ -434,6 +536,9 @@ def main():
     ap.add_argument("--deep", action="store_true", help="run the deep-sample leg only")
     ap.add_argument("--chroma", action="store_true", help="run the 4:2:2 / 4:4:4 leg only")
     ap.add_argument("--bands", action="store_true", help="run the row-band leg only")
+    ap.add_argument("--layout", action="store_true", help="run the semi-planar (NV12 / P010) leg only")
+    ap.add_argument("--planar_only", action="store_true", help="--layout: the planar paths alone")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_bench_nv12.txt"), help="--layout: file the lines are appended to")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("video_bench needs the MI355X")
@@ -447,6 +552,9 @@ def main():
         return
     if args.chroma:
         chroma_leg(sd, args.rounds, args.replays)
+        return
+    if args.layout:
+        layout_leg(sd, min(args.rounds, 5), args.replays, args.planar_only, args.out)
         return
     if args.bands:
         for mode in args.modes.split(","):
