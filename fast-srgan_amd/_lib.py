@@ -21,6 +21,7 @@ YUV_BT601, YUV_BT709 = 0, 1                 # fsr_conv_desc.yuv_matrix, fsr_i420
 SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_image's input
 CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr_*_yuv entry points
 LAYOUT_PLANAR, LAYOUT_NV12 = 0, 1                # payload layout of the fsr_*_yuv_ex entry points
+BLUR_MAX_RADIUS, BLUR_TAPS = 9, 19               # fsr_degrade_blur_noise
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
 ABI_VERSION = 16
 
@@ -117,6 +118,8 @@ SIGNATURES = {
     "fsr_loss_scale_update": (c_int, [P, c_float, c_float, c_float, P]),
     "fsr_crop_resize": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P]),
     "fsr_copy_rows": (c_int, [P, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "fsr_degrade_blur_noise": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
+    "fsr_jpeg_roundtrip": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P]),
 }
 
 _lib = None

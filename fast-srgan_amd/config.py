@@ -11,6 +11,11 @@ and the fp16 loss scaler:
   skips BOTH optimizer updates of the iteration and halves the scale; `training.loss_scale_growth_interval` (default 1000,
   >= 1) clean iterations double it.  With `false` the scale is static.
 
+`data.degradation.{blur_sigma, blur_prob, noise_sigma, noise_prob, jpeg_quality, jpeg_prob, jpeg_subsampling}`: random
+degradation of the LR batches on the device.  The keys are NOT in configs/config.yaml (it keeps the reference's keys and values) and
+have no entry in DEFAULTS: train.make_degradation reads them with defaults of "off", and an override of a key the file lacks
+(`data.degradation.jpeg_prob=0.7`, `data.degradation.jpeg_quality=[30,95]`) creates the groups on its way.
+
 hydra run directory (/root/reference/train.py:46 is `@hydra.main(version_base="1.1", ...)`, under which hydra changes the
 working directory to `outputs/<date>/<time>` before `main` runs, so `runs/...` checkpoints land there): `enter_run_dir`
 reproduces that, including hydra's own override keys `hydra.run.dir=<path>` and `hydra.job.chdir=false`.

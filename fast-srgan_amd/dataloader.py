@@ -7,6 +7,7 @@ down-scale / [-1,1] mapping run in two HIP kernels (csrc/data.hip) instead of 16
 `DeviceBatchLoader` draws whole batches that way (what train.py's RandomSampler(replacement=True) +
 DataLoader pair does, train.py:69-113) and is what the Trainer iterates.
 """
+import collections
 import math
 import random
 
@@ -14,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import ops
 from .ops import _p, _stream
 
 
@@ -47,6 +49,70 @@ def aa_bicubic_taps(in_size, out_size):
     return xmin, xsize, w, kmax
 
 
+DegradeParams = collections.namedtuple("DegradeParams", "blur_sigma noise_sigma seeds quality")   # lists of n; 0 = the stage is off
+
+
+class Degradation:
+    """Random degradation of the LR batch on the device: LR = JPEG(blur(LR) + noise), each stage with its own probability and a
+    strength drawn uniformly per sample (csrc/degrade.hip).  blur_sigma in LR pixels (0 < sigma <= 3), noise_sigma in
+    8-bit code units (<= 25), jpeg_quality integers in 1..100.  The draws come from this object's OWN random.Random: the crop and index
+    streams of DeviceBatchLoader do not move when it is switched on."""
+
+    def __init__(self, blur_sigma=(0.2, 2.0), blur_prob=0., noise_sigma=(1.0, 10.0), noise_prob=0., jpeg_quality=(30, 95), jpeg_prob=0.,
+                 jpeg_subsampling="420", seed=0):
+        self.blur_sigma, self.noise_sigma = tuple(float(v) for v in blur_sigma), tuple(float(v) for v in noise_sigma)
+        self.jpeg_quality = tuple(int(v) for v in jpeg_quality)
+        self.blur_prob, self.noise_prob, self.jpeg_prob = float(blur_prob), float(noise_prob), float(jpeg_prob)
+        self.jpeg_subsampling = str(jpeg_subsampling)
+        for name, (lo, hi), top in (("blur_sigma", self.blur_sigma, ops.BLUR_SIGMA_MAX), ("noise_sigma", self.noise_sigma, ops.NOISE_SIGMA_MAX),
+                                    ("jpeg_quality", self.jpeg_quality, 100)):
+            if len(getattr(self, name)) != 2 or not 0 < lo <= hi <= top:
+                raise ValueError("Degradation: %s must be a (lo, hi) pair with 0 < lo <= hi <= %g, got %r" % (name, top, getattr(self, name)))
+        for name in ("blur_prob", "noise_prob", "jpeg_prob"):
+            if not 0.0 <= getattr(self, name) <= 1.0:
+                raise ValueError("Degradation: %s must be a probability, got %r" % (name, getattr(self, name)))
+        if self.jpeg_subsampling not in ops.JPEG_SUBSAMPLINGS:
+            raise ValueError("Degradation: jpeg_subsampling must be one of %s, got %r" % (ops.JPEG_SUBSAMPLINGS, jpeg_subsampling))
+        self.seed = seed
+        self.rng = random.Random(seed)
+
+    @property
+    def enabled(self):
+        return self.blur_prob > 0 or self.noise_prob > 0 or self.jpeg_prob > 0
+
+    def draw(self, n):
+        """Per-sample parameters of a batch of n.  Order per sample: blur decision, sigma, noise decision, sigma_n, two seed words, JPEG
+        decision, q -- every draw is made whether or not its stage fires, so one stage's probability does not shift another's values."""
+        p = DegradeParams([], [], [], [])
+        rng = self.rng
+        for _ in range(n):
+            on, s = rng.random() < self.blur_prob, rng.uniform(*self.blur_sigma)
+            p.blur_sigma.append(s if on else 0.0)
+            on, s = rng.random() < self.noise_prob, rng.uniform(*self.noise_sigma)
+            p.noise_sigma.append(s if on else 0.0)
+            p.seeds.append((rng.getrandbits(32), rng.getrandbits(32)))
+            on, q = rng.random() < self.jpeg_prob, rng.randint(*self.jpeg_quality)
+            p.quality.append(q if on else 0)
+        return p
+
+    def words(self, params):
+        """The parameters as the int32 words the kernels read (ops.degrade_words), ready for one host-to-device copy."""
+        return ops.degrade_words(len(params.quality), params.blur_sigma, params.noise_sigma, params.seeds, params.quality)
+
+    def apply(self, lr, params, dev_words=None):
+        """Runs the stages on lr (N,3,l,l): at most two launches for blur + noise, one for JPEG.  Which launches run depends on the
+        probabilities alone, never on the draw: a sample whose stage did not fire is copied by the same launch.  `dev_words`:
+        words(params) already on the device (the loader sends them with the batch descriptors); else one pinned, non-blocking copy is
+        made here."""
+        if dev_words is None:
+            dev_words = ops.upload_words(self.words(params), lr.device)
+        if self.blur_prob > 0 or self.noise_prob > 0:
+            lr = ops.degrade_blur_noise_dev(lr, dev_words, blur=self.blur_prob > 0, noise=self.noise_prob > 0)
+        if self.jpeg_prob > 0:
+            lr = ops.jpeg_roundtrip_dev(lr, dev_words, self.jpeg_subsampling)
+        return lr
+
+
 class NumpyImagesDataset(torch.utils.data.Dataset):
     def __init__(self, numpy_paths, lr_image_size, scale_factor, device="cuda"):
         self.numpy_paths = list(numpy_paths)
@@ -78,22 +144,28 @@ class NumpyImagesDataset(torch.utils.data.Dataset):
         _, h, w = self._image(idx).shape
         return rng.randint(0, h - self.hr_image_size), rng.randint(0, w - self.hr_image_size)
 
-    def batch(self, indices, crops):
+    def batch(self, indices, crops, degrade=None):
         """(lr, hr) float32 NCHW device batches for image `indices` cropped at `crops` [(y, x), ...].
         The per-sample descriptors (image pointer, height, width, crop origin) travel as ONE pinned, non-blocking
-        host-to-device copy; nothing here waits for the device."""
+        host-to-device copy; nothing here waits for the device.
+        degrade: a (Degradation, parameters it drew for this batch) pair -- lr then goes through its stages; the parameter
+        words ride at the end of the same copy."""
         n = len(indices)
         imgs = [self._image(i) for i in indices]
-        # [n int64 pointers][4 x n int32: heights, widths, crop_y, crop_x]  (viewed as int64 words for one copy)
-        desc = np.empty(3 * n, dtype=np.int64)
+        # [n int64 pointers][4 x n int32: heights, widths, crop_y, crop_x][degradation words]  (viewed as int64 words for one copy)
+        words = degrade[0].words(degrade[1]) if degrade is not None else None
+        extra = 0 if words is None else words.size // 2              # ops.DEGRADE_WORDS is even
+        desc = np.empty(3 * n + extra, dtype=np.int64)
         desc[:n] = [im.data_ptr() for im in imgs]
-        desc[n:].view(np.int32)[:] = ([im.shape[1] for im in imgs] + [im.shape[2] for im in imgs]
-                                      + [c[0] for c in crops] + [c[1] for c in crops])
+        desc[n:3 * n].view(np.int32)[:] = ([im.shape[1] for im in imgs] + [im.shape[2] for im in imgs]
+                                           + [c[0] for c in crops] + [c[1] for c in crops])
+        if extra:
+            desc[3 * n:].view(np.int32)[:] = words
         host = torch.from_numpy(desc)
         if self.device.type == "cuda":
             host = host.pin_memory()
         dev_desc = host.to(self.device, non_blocking=True)
-        meta = dev_desc[n:].view(torch.int32).view(4, n)
+        meta = dev_desc[n:3 * n].view(torch.int32).view(4, n)
         hr, lr = self.hr_image_size, self.lr_image_size
         hr_out = torch.empty((n, 3, hr, hr), dtype=torch.float32, device=self.device)
         lr_out = torch.empty((n, 3, lr, lr), dtype=torch.float32, device=self.device)
@@ -101,6 +173,8 @@ class NumpyImagesDataset(torch.utils.data.Dataset):
         L.check(L.lib().fsr_crop_resize(_p(dev_desc), _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(meta[3]), n, hr,
                                         self.scale_factor, _p(self._w), _p(self._xmin), _p(self._xsize), self._kmax,
                                         _p(hr_out), _p(lr_out), _p(tmp), _stream()), "fsr_crop_resize")
+        if degrade is not None:
+            lr_out = degrade[0].apply(lr_out, degrade[1], dev_desc[3 * n:].view(torch.int32))
         return lr_out, hr_out
 
     def __getitem__(self, idx):
@@ -115,10 +189,12 @@ class DeviceBatchLoader:
     seeded torch.Generator (RandomSampler(replacement=True)), crops from a seeded `random.Random` (train.py:40-43 seeds
     python's RNG per worker).  sequential=True (validation, train.py:81-91: shuffle=False, drop_last=True): ONE pass over
     the data set in order, len(dataset) // batch_size batches, fresh random crops.  Under data parallelism each rank
-    passes seed + rank."""
+    passes seed + rank.  degradation: a Degradation (with its own seed) applied to every lr batch; None, or one whose
+    probabilities are all 0, leaves every batch and every launch as it is."""
 
-    def __init__(self, dataset, batch_size, iterations=None, seed=1234, sequential=False):
+    def __init__(self, dataset, batch_size, iterations=None, seed=1234, sequential=False, degradation=None):
         self.dataset, self.batch_size, self.sequential = dataset, batch_size, sequential
+        self.degradation = degradation if degradation is not None and degradation.enabled else None
         self.iterations = len(dataset) // batch_size if sequential else iterations
         if self.iterations is None:
             raise ValueError("DeviceBatchLoader needs `iterations` unless sequential=True")
@@ -141,4 +217,7 @@ class DeviceBatchLoader:
             else:
                 idx = torch.randint(len(self.dataset), (self.batch_size,), generator=self.gen).tolist()
             crops = [self.dataset.draw_crop(i, self.rng) for i in idx]
-            yield self.dataset.batch(idx, crops)
+            if self.degradation is None:
+                yield self.dataset.batch(idx, crops)
+            else:
+                yield self.dataset.batch(idx, crops, (self.degradation, self.degradation.draw(len(idx))))

@@ -7,9 +7,11 @@ enqueued on torch's current stream; nothing here synchronises, allocates pinned 
 back to a torch implementation of the math.
 """
 import ctypes
+import math
 import os
 import weakref
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1385,3 +1387,128 @@ def resample_image(t_nhwc, out_h, out_w, kind="f32", matrix="bt601", full_range=
 
 
 PROFILE_RESAMPLE = None   # a list: every resample_image launch appends (start event, end event, algorithmic bytes) -- tools/video_bench.py
+
+
+# ------------------------------------------------------------------ training degradations (csrc/degrade.hip)
+BLUR_SIGMA_MAX, NOISE_SIGMA_MAX = 3.0, 25.0
+JPEG_SUBSAMPLINGS = ("420", "444")
+DEGRADE_WORDS = L.BLUR_TAPS + 5      # 4-byte words per sample: the taps, the radius, the noise sigma, two seed words, the quality
+
+
+def gaussian_taps(sigma):
+    """(radius, float32 taps j = -r..r) of the blur contract: r = min(ceil(3 sigma), 9), exp(-j^2 / 2 sigma^2) normalised in float64 on
+    the host and cast to float32 -- the device never calls exp.  sigma = 0: the identity (r = 0)."""
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= BLUR_SIGMA_MAX:
+        raise ValueError("blur sigma must lie in [0, %g] (0 = off), got %r" % (BLUR_SIGMA_MAX, sigma))
+    if sigma == 0.0:
+        return 0, np.ones(1, dtype=np.float32)
+    r = min(int(math.ceil(3.0 * sigma)), L.BLUR_MAX_RADIUS)
+    j = np.arange(-r, r + 1, dtype=np.float64)
+    w = np.exp(-(j * j) / (2.0 * sigma * sigma))
+    return r, (w / w.sum()).astype(np.float32)
+
+
+def _per_sample(v, n, what):
+    if isinstance(v, torch.Tensor):
+        v = v.tolist()
+    v = list(v)
+    if len(v) != n:
+        raise ValueError("%s: expected %d per-sample values, got %d" % (what, n, len(v)))
+    return v
+
+
+def degrade_words(n, blur_sigma=None, noise_sigma=None, seeds=None, quality=None):
+    """The per-sample parameters of both degradation entry points as ONE int32 array of DEGRADE_WORDS * n words, so that they travel in a
+    single host-to-device copy: [taps: 19 n float32][radii: n int32][noise sigma: n float32][seeds: 2 n uint32][quality: n int32].
+    A stage that is not given stays "off" (radius 0, sigma 0, quality 0).  Ranges are checked here: the C entry points only see pointers."""
+    T = L.BLUR_TAPS
+    words = np.zeros(DEGRADE_WORDS * n, dtype=np.int32)
+    if blur_sigma is not None:
+        taps = words[:T * n].view(np.float32).reshape(n, T)
+        for i, s in enumerate(_per_sample(blur_sigma, n, "blur_sigma")):
+            r, t = gaussian_taps(s)
+            taps[i, :2 * r + 1] = t
+            words[T * n + i] = r
+    if noise_sigma is not None:
+        sig = [float(s) for s in _per_sample(noise_sigma, n, "noise_sigma")]
+        if any(not 0.0 <= s <= NOISE_SIGMA_MAX for s in sig):
+            raise ValueError("noise sigma must lie in [0, %g] code units (0 = off), got %r" % (NOISE_SIGMA_MAX, sig))
+        words[(T + 1) * n:(T + 2) * n].view(np.float32)[:] = sig
+        if seeds is None:
+            raise ValueError("noise needs one (s0, s1) pair of 32-bit seed words per sample")
+        sd = np.array(_per_sample(seeds, n, "seeds"), dtype=np.int64).reshape(n, 2)
+        if sd.min() < 0 or sd.max() > 0xffffffff:
+            raise ValueError("seed words must be unsigned 32-bit integers")
+        words[(T + 2) * n:(T + 4) * n].view(np.uint32)[:] = sd.reshape(-1).astype(np.uint32)
+    if quality is not None:
+        q = [int(v) for v in _per_sample(quality, n, "quality")]
+        if any(not 0 <= v <= 100 for v in q):
+            raise ValueError("JPEG quality must lie in 0..100 (0 = off), got %r" % (q,))
+        words[(T + 4) * n:] = q
+    return words
+
+
+def upload_words(words, device):
+    """One pinned, non-blocking host-to-device copy of a small parameter array; nothing waits for the device."""
+    host = torch.from_numpy(words)
+    if torch.device(device).type == "cuda":
+        host = host.pin_memory()
+    return host.to(device, non_blocking=True)
+
+
+def _check_degrade_input(x, who):
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+        raise ValueError("%s expects a contiguous float32 (N,3,H,W) tensor, got %s %s" % (who, x.dtype, tuple(x.shape)))
+    if x.requires_grad:
+        raise ValueError("%s has no autograd: it is a data-path operator, detach the input" % who)
+    _check_dev(x)
+
+
+def degrade_blur_noise_dev(x, dev_words, blur=True, noise=True):
+    """fsr_degrade_blur_noise with the parameters already on the device (`dev_words`: degrade_words(...) uploaded).  blur=False is the
+    noise-only launch, noise=False the blur alone; the launches depend on these two flags only, never on the values drawn."""
+    _check_degrade_input(x, "degrade_blur_noise")
+    if not (blur or noise):
+        raise ValueError("degrade_blur_noise: neither blur nor noise asked for")
+    n, _, h, w = x.shape
+    if dev_words.dtype != torch.int32 or dev_words.numel() != DEGRADE_WORDS * n or dev_words.device != x.device:
+        raise ValueError("degrade_blur_noise: dev_words must hold %d int32 words on %s" % (DEGRADE_WORDS * n, x.device))
+    base, T = dev_words.data_ptr(), L.BLUR_TAPS
+    out = torch.empty_like(x)
+    tmp = torch.empty_like(x) if blur else None
+    L.check(L.lib().fsr_degrade_blur_noise(_p(x), _p(out), _p(tmp), n, h, w, base if blur else None, base + 4 * T * n if blur else None,
+                                           base + 4 * (T + 1) * n if noise else None, base + 4 * (T + 2) * n if noise else None, _stream()),
+            "fsr_degrade_blur_noise")
+    return out
+
+
+def jpeg_roundtrip_dev(x, dev_words, subsampling="420"):
+    """fsr_jpeg_roundtrip with the qualities already on the device (the last n words of `dev_words`)."""
+    _check_degrade_input(x, "jpeg_roundtrip")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("jpeg_roundtrip: subsampling must be one of %s, got %r" % (JPEG_SUBSAMPLINGS, subsampling))
+    n, _, h, w = x.shape
+    if dev_words.dtype != torch.int32 or dev_words.numel() != DEGRADE_WORDS * n or dev_words.device != x.device:
+        raise ValueError("jpeg_roundtrip: dev_words must hold %d int32 words on %s" % (DEGRADE_WORDS * n, x.device))
+    out = torch.empty_like(x)
+    L.check(L.lib().fsr_jpeg_roundtrip(_p(x), _p(out), n, h, w, dev_words.data_ptr() + 4 * (L.BLUR_TAPS + 4) * n, chroma_code(subsampling),
+                                       _stream()), "fsr_jpeg_roundtrip")
+    return out
+
+
+def degrade_blur_noise(x, blur_sigma, noise_sigma, seeds):
+    """Gaussian blur, then additive Gaussian noise, on a float32 (N,3,H,W) batch in [-1,1].  Per sample (sequences or
+    tensors of length N): blur_sigma in LR pixels, 0 < sigma <= 3; noise_sigma in 8-bit code units, 0 < sigma <= 25; seeds, one (s0, s1)
+    pair of 32-bit words that names the sample's noise field.  0 switches a stage off for a sample (it is copied); None switches it off
+    for the call (noise only: one launch; blur only: two).  No autograd."""
+    _check_degrade_input(x, "degrade_blur_noise")
+    words = degrade_words(x.shape[0], blur_sigma=blur_sigma, noise_sigma=noise_sigma, seeds=seeds)
+    return degrade_blur_noise_dev(x, upload_words(words, x.device), blur=blur_sigma is not None, noise=noise_sigma is not None)
+
+
+def jpeg_roundtrip(x, quality, subsampling="420"):
+    """What a baseline JPEG encode + decode does to a float32 (N,3,H,W) batch in [-1,1], without the entropy coder:
+    per-sample integer quality 1..100 (libjpeg's table scaling; 0 copies the sample), subsampling "420" or "444".  No autograd."""
+    _check_degrade_input(x, "jpeg_roundtrip")
+    return jpeg_roundtrip_dev(x, upload_words(degrade_words(x.shape[0], quality=quality), x.device), subsampling)

@@ -14,7 +14,7 @@ import torch
 
 from . import distributed as D
 from .config import enter_run_dir, hydra_run_settings, load_config
-from .dataloader import DeviceBatchLoader, NumpyImagesDataset
+from .dataloader import Degradation, DeviceBatchLoader, NumpyImagesDataset
 from .trainer import Trainer
 
 
@@ -58,6 +58,33 @@ def write_images_to_numpy_arrays(image_list, output_dir, threads=16):
             list(executor.map(lambda t: _write(*t), todo))
 
 
+def make_degradation(config, seed_value):
+    """The Degradation of one loader from data.degradation.* (every key optional, everything off by default); None when every
+    probability is 0, so that such a run builds the loaders it always built."""
+    node = getattr(config.data, "degradation", None)
+    keys = ("blur_sigma", "blur_prob", "noise_sigma", "noise_prob", "jpeg_quality", "jpeg_prob", "jpeg_subsampling")
+    given = {} if node is None else {k: v for k, v in vars(node).items() if v is not None}
+    unknown = sorted(set(given) - set(keys))
+    if unknown:
+        raise ValueError("unknown data.degradation key(s) %s (known: %s)" % (unknown, ", ".join(keys)))
+    if "jpeg_subsampling" in given:
+        given["jpeg_subsampling"] = str(given["jpeg_subsampling"])          # YAML reads 420 as an integer
+    deg = Degradation(seed=seed_value, **given)
+    return deg if deg.enabled else None
+
+
+def build_loaders(config, dataset, rank=0):
+    """(validation, pre-training, training) loaders; seeds derive from experiment.seed and the rank, the degradations' too."""
+    bs, base = config.training.batch_size, config.experiment.seed
+    val = DeviceBatchLoader(dataset, bs, seed=base + 7919 * (rank + 1), sequential=True,                 # train.py:81-91
+                            degradation=make_degradation(config, base + 15485863 * (rank + 1)))
+    pre = DeviceBatchLoader(dataset, bs, config.training.pretrain_iterations, seed=base + rank,
+                            degradation=make_degradation(config, base + 32452843 * (rank + 1)))
+    trn = DeviceBatchLoader(dataset, bs, config.training.iterations, seed=base + 104729 * (rank + 1),
+                            degradation=make_degradation(config, base + 49979687 * (rank + 1)))
+    return val, pre, trn
+
+
 def main(argv=None, config_dir="configs"):
     argv = sys.argv[1:] if argv is None else list(argv)
     config = load_config(os.path.join(config_dir, "config.yaml"), argv)
@@ -85,10 +112,7 @@ def main(argv=None, config_dir="configs"):
     seed(config.experiment.seed + rank)
     numpy_files = sorted(os.path.join(config.data.numpy_dir, x) for x in os.listdir(config.data.numpy_dir) if x.endswith(".npy"))
     dataset = NumpyImagesDataset(numpy_files, config.data.lr_image_size, config.data.scale_factor, device=config.training.device)
-    bs = config.training.batch_size
-    val = DeviceBatchLoader(dataset, bs, seed=config.experiment.seed + 7919 * (rank + 1), sequential=True)   # train.py:81-91
-    pre = DeviceBatchLoader(dataset, bs, config.training.pretrain_iterations, seed=config.experiment.seed + rank)
-    trn = DeviceBatchLoader(dataset, bs, config.training.iterations, seed=config.experiment.seed + 104729 * (rank + 1))
+    val, pre, trn = build_loaders(config, dataset, rank)
     trainer = Trainer(config)
     trainer.pretrain(pre, val)
     trainer.train(trn, val)

@@ -434,6 +434,30 @@ int fsr_crop_resize(const uint8_t* const* images, const int* img_h, const int* i
                     const int* crop_x, int n, int hr_size, int scale, const float* wtab, const int* xmin,
                     const int* xsize, int kmax, float* hr_out, float* lr_out, float* tmp, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ training degradations (added within ABI 16: new entry points only)
+ * Both work on float NCHW batches [n,3,h,w] in [-1,1] (what fsr_crop_resize writes); every per-sample array is a DEVICE pointer.
+ *
+ * fsr_degrade_blur_noise: separable Gaussian blur (horizontal pass in -> tmp, vertical pass tmp -> out), then additive noise in the
+ * vertical pass's epilogue: two launches.  taps: float [n][FSR_BLUR_TAPS], sample i uses taps[i][0 .. 2 radii[i]] for the offsets
+ * j = -radii[i] .. radii[i] (built and normalised on the host), float accumulation in that order, source index clamped at the borders;
+ * radii[i] = 0 copies the sample (radii above FSR_BLUR_MAX_RADIUS are read as that).  noise_sigma: float [n] in 8-bit code units, 0 =
+ * none; element e = (c h + y) w + x of sample i gets x += z * noise_sigma[i] * (2 / 255) with z = sqrtf(-2 logf(U1)) cosf(6.2831855f U2),
+ * U1 = ((a >> 8) + 1) 2^-24, U2 = (b >> 8) 2^-24, a = mix32(mix32(s0 + 2e) ^ s1), b = mix32(mix32(s0 + 2e + 1) ^ s1), (s0, s1) =
+ * seeds[2i], seeds[2i + 1], mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ * taps = radii = NULL: the noise-only form, one launch in -> out (tmp unused, may be NULL).  noise_sigma = seeds = NULL: blur only.
+ * in == out is allowed; tmp must be a third buffer of the same size.
+ *
+ * fsr_jpeg_roundtrip: what a baseline JPEG encode + decode at quality[i] (int [n], 1..100, libjpeg's scaling of the Annex K tables;
+ * 0 copies the sample, values above 100 are read as 100) does to sample i, without the entropy coder: one launch, one workgroup per
+ * 16x16 pixels.  subsampling: FSR_CHROMA_420 (2x2 chroma mean, replicated back) or FSR_CHROMA_444.  The input code (x + 1) 127.5 is
+ * clamped to [0, 255] but NOT rounded; the output is clamp(rint(.), 0, 255) / 127.5 - 1.
+ * Refused (-1 / -2, nothing launched): null pointers, n, h or w < 1, 3 h w >= 2^31, an unknown subsampling. */
+#define FSR_BLUR_MAX_RADIUS 9
+#define FSR_BLUR_TAPS 19
+int fsr_degrade_blur_noise(const float* in, float* out, float* tmp, int n, int h, int w, const float* taps, const int* radii,
+                           const float* noise_sigma, const unsigned* seeds, fsr_stream_t stream);
+int fsr_jpeg_roundtrip(const float* in, float* out, int n, int h, int w, const int* quality, int subsampling, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ strided row-block copy (ABI 15; the banded tail)
  * A frame of H2 rows is covered by nwin = ceil(H2 / R) windows of Hw >= R + 4 rows: window k owns the core rows
  * [k R, min((k + 1) R, H2)) and starts at row s_k = clamp(k R - 2, 0, H2 - Hw).  The windows of all images are numbered
