@@ -385,6 +385,38 @@ def test_c_abi_rejects_malformed_calls(dev):
     assert lib.fsr_pack_conv3x3(L.FSR_F32, 9, p, 16, 16, 16, p, None) < 0
 
 
+def test_c_abi_rejects_malformed_elementwise_loss_and_optimiser_calls(dev):
+    """Channel counts that do not tile a 256-thread workgroup (24 f32 channels = 6 units), odd pooling extents, null pointers and
+    zero counts of the loss and AdamW calls: a negative code and a message, nothing enqueued."""
+    lib = L.lib()
+    buf = torch.zeros(1 << 16).to(dev)
+    p = buf.data_ptr()
+    f32 = L.FSR_F32
+    refused = [
+        lib.fsr_instnorm_act_fwd(f32, p, p, None, L.ACT_NONE, 0.0, None, p, 1, 64, 24, None),
+        lib.fsr_instnorm_act_bwd_reduce(f32, p, p, p, L.ACT_NONE, 0.0, None, p, None, p, 1, 64, 24, None),
+        lib.fsr_instnorm_act_bwd_apply(f32, p, p, p, p, L.ACT_NONE, 0.0, None, p, 1, 64, 24, None),
+        lib.fsr_conv1x1_c1_bwd(f32, p, p, p, p, p, p, p, 8, 24, None),
+        lib.fsr_maxpool2_fwd(f32, p, p, p, 1, 8, 7, 16, None),
+        lib.fsr_maxpool2_bwd_argmax(f32, p, p, p, 1, 7, 8, 16, 0, None),
+        lib.fsr_maxpool2_bwd(f32, p, p, p, p, 1, 8, 7, 16, 1, None),
+        lib.fsr_bce_logits_fwd(None, p, p, p, 64, None), lib.fsr_bce_logits_fwd(p, p, p, p, 0, None),
+        lib.fsr_bce_logits_bwd(p, p, None, p, 64, None), lib.fsr_bce_logits_bwd(p, p, p, p, 0, None),
+        lib.fsr_smooth_l1_fwd(f32, p, None, p, p, 64, None), lib.fsr_smooth_l1_fwd(f32, p, p, p, p, 0, None),
+        lib.fsr_smooth_l1_bwd(f32, p, p, p, None, 64, None), lib.fsr_smooth_l1_bwd(f32, p, p, p, p, 0, None),
+        lib.fsr_adamw_step(p, None, p, p, 64, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, 1.0, None),
+        lib.fsr_adamw_step(p, p, p, p, 64, 1e-3, 0.9, 0.999, 1e-8, 0.0, None, 1.0, None),
+        lib.fsr_adamw_step_scaled(p, p, p, p, 64, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, 1.0, None, None),
+        lib.fsr_adamw_step_scaled(p, p, p, p, 0, 1e-3, 0.9, 0.999, 1e-8, 0.0, p, 1.0, p, None),
+        lib.fsr_grad_nonfinite(p, 0, p, None), lib.fsr_grad_nonfinite(None, 64, p, None),
+        lib.fsr_loss_scale_update(None, 3.0, 2.0, 0.5, None), lib.fsr_loss_scale_update(p, 0.5, 2.0, 0.5, None)]
+    assert all(rc < 0 for rc in refused), refused
+    assert len(lib.fsr_last_error()) > 0
+    assert lib.fsr_instnorm_act_fwd(f32, p, p, None, L.ACT_NONE, 0.0, None, p, 1, 64, 24, None) < 0 and b"tile" in lib.fsr_last_error()
+    assert lib.fsr_maxpool2_bwd(f32, p, p, p, p, 1, 8, 7, 16, 1, None) < 0 and b"odd extent" in lib.fsr_last_error()
+    assert float(buf.abs().sum()) == 0.0          # nothing ran
+
+
 def test_first_layer_kernels_reject_bad_arguments(dev):
     cd = ops.Compute("f32")
     lib = L.lib()
