@@ -153,9 +153,9 @@ def test_float32_contract_is_inside_the_cap():
 
 
 # -------------------------------------------------------------------------------------------------- 5. JPEG on arbitrary inputs
-# Fixture seeds chosen so that the contract alone leaves out at most a quarter of the pixels at q = 10 (0, 11, 23 and 0 % here): a small
-# picture has few blocks, and one coefficient near a tie takes a whole 16x16 MCU out.
-ARBITRARY_SEED = {(8, 8): 0, (24, 24): 14, (40, 56): 4, (17, 9): 2}
+# Fixture seeds chosen so that the contract alone leaves out at most a quarter of the pixels at q = 10 (0, 11, 23, 0, 0, 24 and 23 % here):
+# a small picture has few blocks, and one coefficient near a tie takes a whole 16x16 MCU out.  The smallest seed that does is taken.
+ARBITRARY_SEED = {(8, 8): 0, (24, 24): 14, (40, 56): 4, (17, 9): 2, (1, 1): 0, (16, 17): 0, (15, 33): 0}
 
 
 def _arbitrary(h, w):
@@ -165,7 +165,7 @@ def _arbitrary(h, w):
 
 
 @pytest.mark.parametrize("sub", ["420", "444"])
-@pytest.mark.parametrize("h,w", [(8, 8), (24, 24), (40, 56), (17, 9)])
+@pytest.mark.parametrize("h,w", [(8, 8), (24, 24), (40, 56), (17, 9), (1, 1), (16, 17), (15, 33)])
 def test_jpeg_arbitrary(dev, h, w, sub):
     x = _arbitrary(h, w)
     skip = C.tie_pixel_mask(x, 10, sub)
