@@ -116,6 +116,7 @@ SIGNATURES = {
     "fsr_grad_nonfinite": (c_int, [P, c_ll, P, P]),
     "fsr_adamw_step_scaled": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, P, c_float, P, P]),
     "fsr_loss_scale_update": (c_int, [P, c_float, c_float, c_float, P]),
+    "fsr_adamw_step_ex": (c_int, [P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, P, c_float, P, c_float, P]),
     "fsr_crop_resize": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P]),
     "fsr_copy_rows": (c_int, [P, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_degrade_blur_noise": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),

@@ -16,6 +16,11 @@ degradation of the LR batches on the device.  The keys are NOT in configs/config
 have no entry in DEFAULTS: train.make_degradation reads them with defaults of "off", and an override of a key the file lacks
 (`data.degradation.jpeg_prob=0.7`, `data.degradation.jpeg_quality=[30,95]`) creates the groups on its way.
 
+`training.lr_schedule.{kind, warmup, milestones, gamma, min_lr}`, `training.ema_decay`, `training.save_state` and `training.resume`
+(learning-rate schedules and a generator EMA that work under hipGraph replay, bit-exact resume) are extension keys of
+the same kind: absent from configs/config.yaml and DEFAULTS, read by the Trainer with defaults of "off".  `training.resume=auto` looks
+under `runs/<experiment.name>/` of the run directory, so it goes with `hydra.run.dir=<the interrupted run's directory>`.
+
 hydra run directory (/root/reference/train.py:46 is `@hydra.main(version_base="1.1", ...)`, under which hydra changes the
 working directory to `outputs/<date>/<time>` before `main` runs, so `runs/...` checkpoints land there): `enter_run_dir`
 reproduces that, including hydra's own override keys `hydra.run.dir=<path>` and `hydra.job.chdir=false`.
@@ -112,6 +117,8 @@ def enter_run_dir(cfg, overrides=(), run_dir=None, create=True):
             setattr(cfg.data, key, os.path.abspath(val))
     if getattr(cfg.training, "vgg19_weights", ""):
         cfg.training.vgg19_weights = os.path.abspath(cfg.training.vgg19_weights)
+    if getattr(cfg.training, "resume", None) and str(cfg.training.resume) != "auto":
+        cfg.training.resume = os.path.abspath(str(cfg.training.resume))
     if not chdir:
         return None
     run_dir = os.path.abspath(run_dir)

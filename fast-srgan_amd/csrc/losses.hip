@@ -9,6 +9,7 @@
 // summed with DPP/shuffle steps, the 4 waves of a workgroup meet in LDS and the workgroup's sum goes to
 // its slot of a scratch buffer; reduce.hip adds the slots in a fixed order (bit-reproducible losses and
 // gradients, no float atomics).
+#include "fsr_adamw.h"
 #include "fsr_common.h"
 #include "fsr_host.h"
 
@@ -168,14 +169,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   const float bc1 = 1.f - powf(b1, t);
   const float rsqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, t));
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);   // torch: exp_avg.lerp_(grad, 1 - beta1)
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    fsr_adamw_update(pi, g[i], gscale, mi, vi, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-    pi -= (lr / bc1) * (mi / denom);
     p[i] = pi;
   }
 }
@@ -201,14 +198,10 @@ __global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p
   const float bc1 = 1.f - powf(b1, t);
   const float rsqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, t));
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-    const float gi = g[i] * gs;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = m[i] + (gi - m[i]) * (1.f - b1);
-    const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    fsr_adamw_update(pi, g[i], gs, mi, vi, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) * rsqrt_bc2 + eps;
-    pi -= (lr / bc1) * (mi / denom);
     p[i] = pi;
   }
 }
@@ -250,6 +243,7 @@ extern "C" int fsr_adamw_step_scaled(float* p, const float* g, float* m, float* 
   hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, g, m, v, count, lr, beta1,
                      beta2, eps, weight_decay, step_counter, grad_scale, scale_state);
   hipLaunchKernelGGL(adamw_tick_if_clean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, step_counter, scale_state);
+  fsr_note_kernel("adamw_scaled_kernel");
   return fsr_check_launch("adamw_scaled_kernel");
 }
 
@@ -396,5 +390,6 @@ extern "C" int fsr_adamw_step(float* p, const float* g, float* m, float* v, long
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, g, m, v, count, lr, beta1,
                      beta2, eps, weight_decay, step_counter, grad_scale);
+  fsr_note_kernel("adamw_kernel");
   return fsr_check_launch("adamw_kernel");
 }

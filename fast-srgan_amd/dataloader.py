@@ -190,7 +190,9 @@ class DeviceBatchLoader:
     python's RNG per worker).  sequential=True (validation, train.py:81-91: shuffle=False, drop_last=True): ONE pass over
     the data set in order, len(dataset) // batch_size batches, fresh random crops.  Under data parallelism each rank
     passes seed + rank.  degradation: a Degradation (with its own seed) applied to every lr batch; None, or one whose
-    probabilities are all 0, leaves every batch and every launch as it is."""
+    probabilities are all 0, leaves every batch and every launch as it is.
+    state_dict() / load_state_dict(): the three random streams and the batches already yielded -- a restored loader yields the
+    REMAINING batches of the interrupted pass, the very ones the uninterrupted loader would have, and then stops."""
 
     def __init__(self, dataset, batch_size, iterations=None, seed=1234, sequential=False, degradation=None):
         self.dataset, self.batch_size, self.sequential = dataset, batch_size, sequential
@@ -206,12 +208,30 @@ class DeviceBatchLoader:
                           "fixed validation images will be skipped (drop_last semantics of train.py:81-91)" % (len(dataset), batch_size))
         self.gen = torch.Generator().manual_seed(seed)
         self.rng = random.Random(seed)
+        self._yielded, self._resume_at = 0, 0
 
     def __len__(self):
         return self.iterations
 
+    def state_dict(self):
+        return {"generator": self.gen.get_state(), "rng": self.rng.getstate(), "yielded": self._yielded,
+                "degradation": None if self.degradation is None else self.degradation.rng.getstate()}
+
+    def load_state_dict(self, sd):
+        if (sd["degradation"] is None) != (self.degradation is None):
+            raise ValueError("DeviceBatchLoader.load_state_dict: the state was saved %s a degradation, this loader runs %s one"
+                             % (("without", "with") if sd["degradation"] is None else ("with", "without")))
+        self.gen.set_state(sd["generator"])
+        self.rng.setstate(sd["rng"])
+        if self.degradation is not None:
+            self.degradation.rng.setstate(sd["degradation"])
+        self._yielded = int(sd["yielded"])
+        self._resume_at = self._yielded if self._yielded < self.iterations or not self.sequential else 0   # a finished validation pass starts over
+
     def __iter__(self):
-        for it in range(self.iterations):
+        start, self._resume_at = self._resume_at, 0
+        for it in range(start, self.iterations):
+            self._yielded = it + 1
             if self.sequential:
                 idx = list(range(it * self.batch_size, (it + 1) * self.batch_size))
             else:

@@ -10,16 +10,41 @@ names) and the same arithmetic per iteration as trainer.py:171-196.  Differences
   * D(hr) and D(G(lr).detach()) of the D step (trainer.py:172,174) run as one batch of 2B images (same weights,
     per-sample ops), and the frozen perceptual branch runs on a second HIP stream;
   * one process per GPU: gradients are averaged across ranks with one RCCL all-reduce per optimizer.
+
+Long runs (extension keys, all off by default): training.lr_schedule.{kind,warmup,milestones,gamma,min_lr} puts both
+optimizers of the GAN phase on a device-side learning-rate schedule (effective under hipGraph replay), training.ema_decay keeps an
+exponential moving average of the generator (Trainer.generator_ema, generator_ema_epoch_N.pt), training.save_state adds
+state_N.pt to every checkpoint and training.resume=<state_N.pt | auto> continues such a run bit for bit.
 """
 import os
 import os.path as osp
+import random
+import re
 
+import numpy as np
 import torch
 
 from . import distributed as D
 from . import ops
 from .model import VGG19, Discriminator, Generator
-from .optim import ArenaAdamW
+from .optim import ArenaAdamW, LRSchedule
+
+_SCHEDULE_KEYS = ("kind", "warmup", "milestones", "gamma", "min_lr")
+
+
+def _schedule_settings(config):
+    """training.lr_schedule.* as LRSchedule arguments (None: no schedule).  Not in configs/config.yaml, like data.degradation.*."""
+    node = getattr(config.training, "lr_schedule", None)
+    if node is None:
+        return None
+    given = {k: v for k, v in (node.items() if isinstance(node, dict) else vars(node).items()) if v is not None}
+    unknown = sorted(set(given) - set(_SCHEDULE_KEYS))
+    if unknown:
+        raise ValueError("unknown training.lr_schedule key(s) %s (known: %s)" % (unknown, ", ".join(_SCHEDULE_KEYS)))
+    if not given:
+        return None
+    given.setdefault("kind", "multistep" if "milestones" in given else "constant")
+    return given
 
 
 class _NullWriter:
@@ -68,7 +93,17 @@ class Trainer:
         self.perceptual_network.eval()
         for p in self.perceptual_network.parameters():
             p.requires_grad = False
-        self.optim_generator = ArenaAdamW(self.generator.parameters(), lr=self.config.training.generator_lr)
+        self._lr_schedule = _schedule_settings(config)
+        if self._lr_schedule is not None:
+            self._schedules()               # bad values are refused here, not when the GAN phase begins
+        self.ema_decay = float(getattr(config.training, "ema_decay", 0.0) or 0.0)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("training.ema_decay must be in [0, 1), got %r" % (self.ema_decay,))
+        self.save_state = bool(getattr(config.training, "save_state", False))
+        self._resume = getattr(config.training, "resume", None) or None
+        self._resume_file = False           # False: not resolved yet; None: a fresh start
+        self.optim_generator = ArenaAdamW(self.generator.parameters(), lr=self.config.training.generator_lr,
+                                          ema_decay=self.ema_decay if self.ema_decay > 0.0 else None)
         self.optim_discriminator = ArenaAdamW(self.discriminator.parameters(), lr=self.config.training.discriminator_lr)
         D.broadcast_parameters(self.optim_generator)
         D.broadcast_parameters(self.optim_discriminator)
@@ -119,6 +154,15 @@ class Trainer:
         self._streams = {}
         self._seed_consts = {}
         self.use_side_stream = os.environ.get("FSR_SIDE_STREAM", "1") != "0"
+        # training.ema_decay: a second Generator whose parameters ARE the optimizer's EMA arena (views, no copies); it has no
+        # buffers (stat-free InstanceNorm), so its state_dict is the EMA weights under the generator's own keys.  Built with the
+        # global RNG put back afterwards: switching the EMA on does not move any later draw.
+        self.generator_ema = None
+        if self.ema_decay > 0.0:
+            with torch.random.fork_rng(devices=[]):
+                self.generator_ema = Generator(config=config.generator, compute_dtype=cdt).to(dev)
+            self.generator_ema.eval()
+            self.optim_generator.attach_ema_params(self.generator_ema.parameters())
         self.loss_fn = ops.bce_with_logits      # torch.nn.BCEWithLogitsLoss(), trainer.py:41
         self.l1_loss = ops.smooth_l1            # torch.nn.SmoothL1Loss(), trainer.py:43
 
@@ -377,18 +421,19 @@ class Trainer:
 
     # ------------------------------------------------------------------ validation metrics, trainer.py:46-69
     @torch.no_grad()
-    def _calculate_metrics_over_dataset(self, dataloader, phase, step):
+    def _calculate_metrics_over_dataset(self, dataloader, phase, step, model=None):
         """SSIM and PSNR over the loader as the reference's torchmetrics objects accumulate them (trainer.py:53-69):
         SSIM(reduction="none") keeps one value per image and logs their mean; PSNR(dim=None) accumulates the squared error
         and the element count of EVERYTHING it saw and logs one global 10 log10(1 / mse).  Both come from one HIP kernel
-        per batch (ops.ssim_sse) reading the generator's output and the HR batch in place."""
-        self.generator.eval()
+        per batch (ops.ssim_sse) reading the generator's output and the HR batch in place.  model: the EMA generator instead."""
+        model = self.generator if model is None else model
+        model.eval()
         ssim_sum = sse = None
         images, elements = 0, 0
         for lr_images, hr_images in dataloader:
             lr_images = lr_images.to(self.config.training.device, non_blocking=True)
             hr_images = hr_images.to(self.config.training.device, non_blocking=True)
-            sr_images = self.generator(lr_images)
+            sr_images = model(lr_images)
             n, c, h, w = hr_images.shape
             r = ops.ssim_sse(sr_images, hr_images)
             part = torch.stack([r[:, 0].sum() / float(c * (h - 10) * (w - 10)), r[:, 1].sum()])
@@ -424,12 +469,13 @@ class Trainer:
         self.writer.add_images(f"{phase}/Bicubic", upsampled, global_step=0)
 
     @torch.no_grad()
-    def _log_generated(self, tag, step):
-        """trainer.py:121-127 / :221-230: the generator on the fixed LR batch."""
+    def _log_generated(self, tag, step, model=None):
+        """trainer.py:121-127 / :221-230: the generator (or `model`: the EMA generator) on the fixed LR batch."""
         if Trainer.fixed_lr_images.ndim == 1:
             return
-        self.generator.eval()
-        generated = (1.0 + self.generator(2.0 * Trainer.fixed_lr_images.to(self.config.training.device) - 1.0)) / 2.0
+        model = self.generator if model is None else model
+        model.eval()
+        generated = (1.0 + model(2.0 * Trainer.fixed_lr_images.to(self.config.training.device) - 1.0)) / 2.0
         self.writer.add_images(tag, generated, global_step=step)
 
     def pretrain(self, train_dataloader, val_dataloader):
@@ -437,6 +483,8 @@ class Trainer:
         # runs/pretrain_generator.pt (:133), so its resume never triggers by itself; a user renames the file to opt in.
         # (Picking up pretrain_generator.pt automatically would make every second experiment in a directory silently skip
         # pre-training with the previous run's generator.)
+        if self.resume_file() is not None:      # training.resume: the GAN phase continues from its state file
+            return
         if osp.exists("runs/pretrain.pt"):
             print("Pretrained model found, skipping pretraining")
             ckpt = torch.load("runs/pretrain.pt", map_location="cpu")
@@ -463,25 +511,125 @@ class Trainer:
             torch.save({"model": self.discriminator.state_dict(), "optimizer": self.optim_discriminator.state_dict()},
                        "runs/pretrain_discriminator.pt")
 
-    def save_checkpoints(self, step):
-        """trainer.py:143-156 file names; rank 0 only under data parallelism."""
+    def save_checkpoints(self, step, train_dataloader=None, val_dataloader=None):
+        """trainer.py:143-156 file names; rank 0 only under data parallelism.  training.ema_decay adds generator_ema_epoch_N.pt
+        (the generator's keys: inference.py and video.py load it unchanged); training.save_state adds state_N.pt, everything
+        training.resume needs -- and, under data parallelism, one state_N.rank<r>.pt per rank with that rank's random streams."""
+        save_dir = osp.join("runs", self.config.experiment.name)
+        if self.save_state and D.is_distributed():
+            os.makedirs(save_dir, exist_ok=True)
+            torch.save(self._rank_state(train_dataloader, val_dataloader), osp.join(save_dir, f"state_{step}.rank{D.rank()}.pt"))
         if not self.is_main:
             return
-        save_dir = osp.join("runs", self.config.experiment.name)
         os.makedirs(save_dir, exist_ok=True)
         torch.save(self.generator.state_dict(), osp.join(save_dir, f"generator_epoch_{step}.pt"))
         torch.save(self.discriminator.state_dict(), osp.join(save_dir, f"discriminator_epoch_{step}.pt"))
         torch.save(self.optim_generator.state_dict(), osp.join(save_dir, f"generator_optim_epoch_{step}.pt"))
         torch.save(self.optim_discriminator.state_dict(), osp.join(save_dir, f"discriminator_optim_epoch_{step}.pt"))
+        if self.generator_ema is not None:
+            torch.save(self.generator_ema.state_dict(), osp.join(save_dir, f"generator_ema_epoch_{step}.pt"))
+        if self.save_state:
+            torch.save({"step": int(step), "generator": self.generator.state_dict(), "discriminator": self.discriminator.state_dict(),
+                        "optim_generator": self.optim_generator.state_dict(), "optim_discriminator": self.optim_discriminator.state_dict(),
+                        "rank_state": self._rank_state(train_dataloader, val_dataloader)}, osp.join(save_dir, f"state_{step}.pt"))
+
+    # ------------------------------------------------------------------ training.save_state / training.resume
+    def _rank_state(self, train_dataloader, val_dataloader):
+        """The random streams of this process and the position of its loaders (tensors and plain tuples only)."""
+        kind, keys, pos, has_gauss, cached = np.random.get_state()
+        dev = torch.device(self.config.training.device)
+        return {"torch": torch.get_rng_state(),
+                "device": torch.cuda.get_rng_state(dev) if dev.type == "cuda" and torch.cuda.is_available() else None,
+                "python": random.getstate(),
+                "numpy": (str(kind), torch.from_numpy(keys.astype(np.int64)), int(pos), int(has_gauss), float(cached)),
+                "train_loader": train_dataloader.state_dict() if hasattr(train_dataloader, "state_dict") else None,
+                "val_loader": val_dataloader.state_dict() if hasattr(val_dataloader, "state_dict") else None}
+
+    def _load_rank_state(self, st, train_dataloader, val_dataloader):
+        torch.set_rng_state(st["torch"])
+        if st["device"] is not None:
+            torch.cuda.set_rng_state(st["device"], torch.device(self.config.training.device))
+        random.setstate(st["python"])
+        kind, keys, pos, has_gauss, cached = st["numpy"]
+        np.random.set_state((kind, keys.numpy().astype(np.uint32), pos, has_gauss, cached))
+        for loader, key in ((train_dataloader, "train_loader"), (val_dataloader, "val_loader")):
+            if st[key] is not None and hasattr(loader, "load_state_dict"):
+                loader.load_state_dict(st[key])
+
+    def resume_file(self):
+        """The state file training.resume names (`auto`: the highest state_N.pt under runs/<experiment.name>/), or None."""
+        if self._resume_file is False:
+            self._resume_file = None
+            if self._resume is not None and str(self._resume) == "auto":
+                save_dir, best = osp.join("runs", self.config.experiment.name), None
+                for name in (os.listdir(save_dir) if osp.isdir(save_dir) else ()):
+                    m = re.fullmatch(r"state_(\d+)\.pt", name)
+                    if m and (best is None or int(m.group(1)) > best):
+                        best = int(m.group(1))
+                if best is None:
+                    print("training.resume=auto: no state_N.pt under %s, starting fresh" % save_dir)
+                else:
+                    self._resume_file = osp.join(save_dir, "state_%d.pt" % best)
+            elif self._resume is not None:
+                if not osp.exists(str(self._resume)):
+                    raise FileNotFoundError("training.resume: %s does not exist" % (self._resume,))
+                self._resume_file = str(self._resume)
+        return self._resume_file
+
+    def load_state(self, path, train_dataloader=None, val_dataloader=None):
+        """Restores a state_N.pt (save_checkpoints with training.save_state); returns N, the step it was written after."""
+        st = torch.load(path, map_location="cpu")
+        for what, opt, key in (("generator", self.optim_generator, "optim_generator"),
+                               ("discriminator", self.optim_discriminator, "optim_discriminator")):
+            saved = sum(int(v["exp_avg"].numel()) for v in st[key]["state"].values())
+            if saved != opt.flat_param.numel() or len(st[key]["state"]) != len(opt._slices):
+                raise ValueError("training.resume: %s holds a %s arena of %d floats in %d tensors, the configured network has %d in %d"
+                                 % (path, what, saved, len(st[key]["state"]), opt.flat_param.numel(), len(opt._slices)))
+        self.generator.load_state_dict(st["generator"])
+        self.discriminator.load_state_dict(st["discriminator"])
+        self.optim_generator.load_state_dict(st["optim_generator"])
+        self.optim_discriminator.load_state_dict(st["optim_discriminator"])
+        for opt in (self.optim_generator, self.optim_discriminator):
+            opt.mark_updated()
+        rank_state = st["rank_state"]
+        if D.is_distributed():
+            rank_state = torch.load(re.sub(r"\.pt$", ".rank%d.pt" % D.rank(), path), map_location="cpu")
+        self._load_rank_state(rank_state, train_dataloader, val_dataloader)
+        return int(st["step"])
+
+    def _schedules(self):
+        """One LRSchedule per optimizer: base_lr its configured rate, total = training.iterations."""
+        total = getattr(self.config.training, "iterations", None)
+        return [LRSchedule(base_lr=float(lr), total=total, **self._lr_schedule)
+                for lr in (self.config.training.generator_lr, self.config.training.discriminator_lr)]
+
+    def install_schedules(self):
+        if self._lr_schedule is not None:
+            for opt, schedule in zip((self.optim_generator, self.optim_discriminator), self._schedules()):
+                opt.set_schedule(schedule)
 
     def train(self, train_dataloader, val_dataloader):
-        self._calculate_metrics_over_dataset(val_dataloader, "GAN", step=0)
+        resume, start = self.resume_file(), 0
+        if resume is None:
+            self._calculate_metrics_over_dataset(val_dataloader, "GAN", step=0)
         # trainer.py:160-162 tests `fixed_lr_images is None`, which never holds (the attribute starts as tensor([])), so a
         # run that skipped pre-training reaches :224 with an empty batch.  Fixed here: the fixed batch is drawn whenever it
         # is still unset.
         if Trainer.fixed_lr_images.ndim == 1:
             self._pre_train_setup(val_dataloader)
             self._log_fixed_images("GAN")
+        if resume is None:
+            # the schedules start with the GAN phase (pre-training ran at the constant rates), and so does the average
+            self.install_schedules()
+            if self.generator_ema is not None:
+                self.optim_generator.reset_ema()
+        else:
+            # everything the next iteration reads comes from the file (after the fixed batch above drew from the validation
+            # loader): global step numbers go on in logs and file names
+            start = self.load_state(resume, train_dataloader, val_dataloader)
+            print("training.resume: continuing %s after step %d" % (resume, start))
+            if self._lr_schedule is not None and self.optim_generator.schedule is None:
+                self.install_schedules()
         self.generator.train()
         self.discriminator.train()
         dev = self.config.training.device
@@ -490,9 +638,9 @@ class Trainer:
         # change: every loader of train.py drops the last partial batch.
         use_graph = bool(getattr(self.config.training, "hip_graph", True)) and str(dev).startswith("cuda") and torch.cuda.is_available()
         graph_shape = None
-        for step, (lr_images, hr_images) in enumerate(train_dataloader, start=1):
+        for step, (lr_images, hr_images) in enumerate(train_dataloader, start=start + 1):
             lr_images, hr_images = lr_images.to(dev, non_blocking=True), hr_images.to(dev, non_blocking=True)
-            if use_graph and graph_shape is None and step == 3:     # steps 1-2 ran eagerly: every lazy buffer exists
+            if use_graph and graph_shape is None and step - start == 3:     # (this run's) steps 1-2 ran eagerly: every lazy buffer exists
                 try:
                     self.capture_train_step(lr_images, hr_images, warmup=0)
                     graph_shape = (tuple(lr_images.shape), tuple(hr_images.shape))
@@ -509,8 +657,13 @@ class Trainer:
                 self.writer.add_scalar("Loss/Discriminator/Fake", losses["loss_fake"], global_step=step)
                 self.writer.add_scalar("Loss/Generator/Adversarial", losses["adv_loss"], global_step=step)
                 self.writer.add_scalar("Loss/Generator/Content", losses["content_loss"], global_step=step)
+                if self._lr_schedule is not None:
+                    self.writer.add_scalar("Loss/LR", self.optim_generator.lr_used(), global_step=step)
             if step % self.config.training.checkpoint_iter == 0:
                 self._log_generated("GAN/Generated", step)
                 self._calculate_metrics_over_dataset(val_dataloader, "GAN", step=step)
-                self.save_checkpoints(step)
+                if self.generator_ema is not None:
+                    self._log_generated("GAN/Generated/EMA", step, model=self.generator_ema)
+                    self._calculate_metrics_over_dataset(val_dataloader, "GAN/EMA", step=step, model=self.generator_ema)
+                self.save_checkpoints(step, train_dataloader, val_dataloader)
                 self.generator.train()

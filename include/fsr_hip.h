@@ -424,6 +424,42 @@ int fsr_adamw_step_scaled(float* p, const float* g, float* m, float* v, long lon
                           fsr_stream_t stream);
 int fsr_loss_scale_update(float* scale_state, float growth_interval, float growth, float backoff, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ AdamW with a device-side learning-rate schedule and a fused EMA
+ * (added within ABI 16: a new entry point only).  fsr_adamw_step / fsr_adamw_step_scaled take the learning rate by value,
+ * so a captured hipGraph replays the rate it was captured with.  Here the rate comes from `sched`, FSR_SCHED_WORDS floats in DEVICE
+ * memory that the host writes when it installs a schedule:
+ *   [0] kind: 0 constant, 1 multistep, 2 cosine     [1] base lr     [2] warm-up length W (0: none)     [3] cosine length T
+ *   [4] min lr     [5] number of boundaries nb <= 8     [6] lr_used: the rate of the last update applied (written by one thread of the
+ *   launch, never read by the update)     [7] clock e: updates applied since the schedule was installed
+ *   [8..15] boundaries, ascending, as float step numbers     [16..24] nb + 1 lr values (the host computes base * gamma^k in double and
+ *   casts; the device never takes a power for the schedule; slots behind nb / nb + 1 are not read).
+ * Counters are floats (the clock as the step counter): exact up to 2^24 steps.
+ * The update applied at clock e (the clock BEFORE it; torch's convention: the first update runs at f(0), milestone k takes effect for
+ * update k + 1) uses
+ *   constant / multistep:  val = values[#{boundaries <= e}]
+ *   cosine:                val = min + 0.5 (base - min) (1 + cosf(pi fminf(e, T) / T))
+ *   lr = e < W ? val ((e + 1) / W) : val
+ * and is, with that lr, exactly fsr_adamw_step's arithmetic (scale_state NULL: step counter and clock both advance by one) or
+ * fsr_adamw_step_scaled's (scale_state given: g' = g*grad_scale/S; while the non-finite flag is up NOTHING changes -- p, m, v, ema,
+ * step counter, clock and lr_used stay bit-identical -- else step counter and clock advance by one).
+ * ema (nullable, `count` floats): after p' is computed, ema += (p' - ema) (1 - ema_decay), ema_decay in [0, 1).
+ * Any float pointers are accepted; 16-byte aligned ones take 128-bit loads and stores. */
+#define FSR_SCHED_WORDS 32
+#define FSR_SCHED_KIND 0
+#define FSR_SCHED_BASE 1
+#define FSR_SCHED_WARMUP 2
+#define FSR_SCHED_TOTAL 3
+#define FSR_SCHED_MIN 4
+#define FSR_SCHED_NB 5
+#define FSR_SCHED_LR_USED 6
+#define FSR_SCHED_CLOCK 7
+#define FSR_SCHED_BOUNDS 8
+#define FSR_SCHED_VALUES 16
+#define FSR_SCHED_MAX_BOUNDARIES 8
+int fsr_adamw_step_ex(float* p, const float* g, float* m, float* v, float* ema, long long count, float* sched, float beta1,
+                      float beta2, float eps, float weight_decay, float* step_counter, float grad_scale, const float* scale_state,
+                      float ema_decay, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ crop + antialiased bicubic down-scale (dataloader.py:24-38)
  * For each of `n` samples: crop hr_size x hr_size at (crop_y[i], crop_x[i]) from the uint8 CHW image
  * image[i] (device pointers, heights/widths per image), hr = crop/127.5 - 1 (float NCHW [n,3,hr,hr]);
