@@ -22,6 +22,7 @@ SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_imag
 CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr_*_yuv entry points
 LAYOUT_PLANAR, LAYOUT_NV12 = 0, 1                # payload layout of the fsr_*_yuv_ex entry points
 BLUR_MAX_RADIUS, BLUR_TAPS = 9, 19               # fsr_degrade_blur_noise
+QUALITY_Y, QUALITY_RGB = 0, 1                    # fsr_quality_u8
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
 ABI_VERSION = 16
 
@@ -112,6 +113,8 @@ SIGNATURES = {
     "fsr_smooth_l1_bwd": (c_int, [c_int, P, P, P, P, c_ll, P]),
     "fsr_ssim_sse_scratch": (c_size_t, [c_int, c_int, c_int]),
     "fsr_ssim_sse": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, P, P, P]),
+    "fsr_quality_u8_scratch": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fsr_quality_u8": (c_int, [P, c_ll, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "fsr_adamw_step": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, P, c_float, P]),
     "fsr_grad_nonfinite": (c_int, [P, c_ll, P, P]),
     "fsr_adamw_step_scaled": (c_int, [P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, P, c_float, P, P]),

@@ -21,6 +21,10 @@ have no entry in DEFAULTS: train.make_degradation reads them with defaults of "o
 the same kind: absent from configs/config.yaml and DEFAULTS, read by the Trainer with defaults of "off".  `training.resume=auto` looks
 under `runs/<experiment.name>/` of the run directory, so it goes with `hydra.run.dir=<the interrupted run's directory>`.
 
+`training.eval_dir` (a directory of HR images), `training.eval_shave` and `training.eval_channel` (whole-image PSNR / SSIM
+by the benchmark protocol, logged at the checkpoints of the GAN phase) are extension keys of the same kind; train.main makes the
+directory absolute before the run directory is entered.
+
 hydra run directory (/root/reference/train.py:46 is `@hydra.main(version_base="1.1", ...)`, under which hydra changes the
 working directory to `outputs/<date>/<time>` before `main` runs, so `runs/...` checkpoints land there): `enter_run_dir`
 reproduces that, including hydra's own override keys `hydra.run.dir=<path>` and `hydra.job.chdir=false`.

@@ -1109,6 +1109,40 @@ def ssim_sse(a, b):
     return out
 
 
+QUALITY_CHANNELS = {"y": (L.QUALITY_Y, 1), "rgb": (L.QUALITY_RGB, 3)}     # name -> (fsr_quality_u8 code, channels)
+
+
+def quality_u8(a, b, shave=0, channel="y"):
+    """Per-image (sum of the SSIM map, sum of squared errors), in code units 0..255, of two (N,H,W,3) uint8 batches with a border
+    of `shave` pixels left out (fsr_quality_u8).  channel "y": BT.601 studio luma; "rgb": the three channels.
+    Each tensor has unit stride on its last axis and stride 3 on W; row and image strides are free, so a [:, :H, :W] slice of
+    larger frames is read in place.  Returns a float32 (N,2) tensor; with (eh, ew) the shaved extent and C the channel count,
+    PSNR = 10 log10(255^2 C eh ew / sse) and SSIM = ssim_sum / (C (eh - 10)(ew - 10))."""
+    _check_dev(a, b)
+    if channel not in QUALITY_CHANNELS:
+        raise ValueError("quality_u8 channel must be one of %s, got %r" % (sorted(QUALITY_CHANNELS), channel))
+    for t in (a, b):
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+            raise ValueError("quality_u8 expects (N,H,W,3) uint8 tensors, got %s %s" % (t.dtype, tuple(t.shape)))
+    if a.shape != b.shape:
+        raise ValueError("quality_u8 expects two batches of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    n, h, w, _ = a.shape
+    shave = int(shave)
+    if not 1 <= n <= 65535:
+        raise ValueError("quality_u8 takes 1 .. 65535 images per call, got shape %s" % (tuple(a.shape),))
+    if shave < 0 or min(h, w) - 2 * shave < 11:
+        raise ValueError("quality_u8: shave %d of shape %s leaves no region of at least 11x11" % (shave, tuple(a.shape)))
+    for t in (a, b):
+        if t.stride(3) != 1 or t.stride(2) != 3 or t.stride(1) < 3 * w or (n > 1 and t.stride(0) < 0):
+            raise ValueError("quality_u8 needs strides (*, >= 3 W, 3, 1), got %s for shape %s" % (t.stride(), tuple(t.shape)))
+    code = QUALITY_CHANNELS[channel][0]
+    out = torch.empty((n, 2), dtype=torch.float32, device=a.device)
+    scr = _workspace(L.lib().fsr_quality_u8_scratch(n, h, w, shave, code), a.device)
+    L.check(L.lib().fsr_quality_u8(_p(a), a.stride(0), a.stride(1), _p(b), b.stride(0), b.stride(1), n, h, w, shave, code,
+                                   _p(out), _p(scr), _stream()), "fsr_quality_u8")
+    return out
+
+
 def u8_to_image(frames):
     """(N,H,W,3) uint8 frames -> float32 (N,3,H,W) VIEW in [-1,1] (x / 127.5 - 1, inference.py:48) of an NHWC buffer: the
     first-layer kernels read it in place through its strides."""

@@ -89,6 +89,8 @@ def main(argv=None, config_dir="configs"):
     argv = sys.argv[1:] if argv is None else list(argv)
     config = load_config(os.path.join(config_dir, "config.yaml"), argv)
     rank, world, local_rank = D.init_from_env()
+    if getattr(config.training, "eval_dir", None):     # (an extension key: made absolute here, before the run directory is entered)
+        config.training.eval_dir = os.path.abspath(str(config.training.eval_dir))
     if torch.cuda.is_available():
         torch.cuda.set_device(local_rank)
     # hydra 1.1 (train.py:46) runs `main` inside outputs/<date>/<time>: rank 0 names the directory, every rank enters it

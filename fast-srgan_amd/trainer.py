@@ -15,6 +15,10 @@ Long runs (extension keys, all off by default): training.lr_schedu
 optimizers of the GAN phase on a device-side learning-rate schedule (effective under hipGraph replay), training.ema_decay keeps an
 exponential moving average of the generator (Trainer.generator_ema, generator_ema_epoch_N.pt), training.save_state adds
 state_N.pt to every checkpoint and training.resume=<state_N.pt | auto> continues such a run bit for bit.
+
+Benchmark evaluation (extension keys, off by default): training.eval_dir=<HR directory>, training.eval_shave and
+training.eval_channel log whole-image PSNR / SSIM by the benchmark protocol at the checkpoints of the GAN phase
+(GAN/Eval/PSNR_Y, GAN/Eval/SSIM_Y, and GAN/EMA/Eval/... for the EMA generator).
 """
 import os
 import os.path as osp
@@ -154,6 +158,7 @@ class Trainer:
         self._streams = {}
         self._seed_consts = {}
         self.use_side_stream = os.environ.get("FSR_SIDE_STREAM", "1") != "0"
+        self._evaluator = None      # training.eval_dir: built at the first checkpoint (_log_benchmark_metrics)
         # training.ema_decay: a second Generator whose parameters ARE the optimizer's EMA arena (views, no copies); it has no
         # buffers (stat-free InstanceNorm), so its state_dict is the EMA weights under the generator's own keys.  Built with the
         # global RNG put back afterwards: switching the EMA on does not move any later draw.
@@ -447,6 +452,31 @@ class Trainer:
                                    global_step=step)
         self.writer.flush()
 
+    @torch.no_grad()
+    def _log_benchmark_metrics(self, step):
+        """training.eval_dir (extension key, off by default): whole-image PSNR / SSIM on the images of that directory by the
+        benchmark protocol (evaluate.Evaluator: mod-crop, luma, shaved border, means of the per-image values), logged as
+        GAN/Eval/PSNR_Y and GAN/Eval/SSIM_Y (training.eval_channel=rgb: _RGB), and as GAN/EMA/Eval/... for the EMA generator.
+        Rank 0 only; the Evaluator (HR uploads, device-made LR images) is built at the first checkpoint and kept.  Runs eagerly,
+        after the optimizers' mark_updated(), and leaves the generator in train() mode."""
+        eval_dir = getattr(self.config.training, "eval_dir", None)
+        if not eval_dir or not self.is_main:
+            return
+        if self._evaluator is None:
+            from .evaluate import Evaluator, list_images
+            self._evaluator = Evaluator(list_images(str(eval_dir)), 2 ** len(self.generator.upsampling),
+                                        shave=getattr(self.config.training, "eval_shave", None),
+                                        channel=str(getattr(self.config.training, "eval_channel", None) or "y"),
+                                        device=self.config.training.device, batch=self.config.training.batch_size)
+        suffix = self._evaluator.channel.upper()
+        for phase, model in (("GAN/Eval", self.generator), ("GAN/EMA/Eval", self.generator_ema)):
+            if model is not None:
+                r = self._evaluator.run(model)
+                self.writer.add_scalar(f"{phase}/PSNR_{suffix}", r["psnr"], global_step=step)
+                self.writer.add_scalar(f"{phase}/SSIM_{suffix}", r["ssim"], global_step=step)
+        self.writer.flush()
+        self.generator.train()
+
     @classmethod
     def _pre_train_setup(cls, dataloader):
         if cls.fixed_lr_images.ndim == 1:
@@ -665,5 +695,6 @@ class Trainer:
                 if self.generator_ema is not None:
                     self._log_generated("GAN/Generated/EMA", step, model=self.generator_ema)
                     self._calculate_metrics_over_dataset(val_dataloader, "GAN/EMA", step=step, model=self.generator_ema)
+                self._log_benchmark_metrics(step)
                 self.save_checkpoints(step, train_dataloader, val_dataloader)
                 self.generator.train()

@@ -400,6 +400,28 @@ int fsr_ssim_sse(const float* a, long long asn, long long asc, long long ash, lo
                  long long bsn, long long bsc, long long bsh, long long bsw, int n, int h, int w, float* out,
                  void* scratch, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ benchmark quality on uint8 frames (added within ABI 16)
+ * The evaluation protocol of the super-resolution literature, per image, in one launch: a, b are n images of h x w interleaved
+ * RGB bytes (pixel stride 3), image i at a + i * a_image_bytes, row y at + y * a_row_bytes; the strides of a and b are
+ * independent (one may be a contiguous batch, the other a cropped view of larger frames).  The region evaluated is rows
+ * shave .. h - shave, columns shave .. w - shave (eh x ew); no byte outside it is read.  Values, float32 in code units 0..255:
+ *   FSR_QUALITY_Y   : y = 16 + (65.481 r + 128.553 g + 24.966 b) / 255, the quotients (float)(65.481 / 255.0) etc. -- BT.601 studio luma
+ *                     (evaluated as 16 + fma(kb, b, fma(kg, g, kr r)): the same bytes give the same value in a and in b);
+ *   FSR_QUALITY_RGB : the three channels as they are.
+ * out[i][1] = sum of squared differences over the region (one channel in Y mode, three in RGB mode);
+ * out[i][0] = sum of the SSIM map (fsr_ssim_sse's window and formula, c1 = (0.01f * 255.f)^2, c2 = (0.03f * 255.f)^2) over the
+ *             (eh - 10) x (ew - 10) windows inside the region and over the channels:
+ *   PSNR_i = 10 log10(255^2 channels eh ew / out[i][1]);  SSIM_i = out[i][0] / (channels (eh - 10)(ew - 10)).
+ * scratch: fsr_quality_u8_scratch(...) bytes (0 for n <= 0 or a region below 11 x 11): [n][channels * tiles][2] partials of
+ * 32 x 32 tiles, added in a fixed order.  Refused with nothing launched: null pointers, n outside 1..65535, an unknown channel,
+ * shave < 0, a region below 11 x 11, a row stride below 3 w. */
+#define FSR_QUALITY_Y 0
+#define FSR_QUALITY_RGB 1
+size_t fsr_quality_u8_scratch(int n, int h, int w, int shave, int channel);
+int fsr_quality_u8(const unsigned char* a, long long a_image_bytes, long long a_row_bytes, const unsigned char* b,
+                   long long b_image_bytes, long long b_row_bytes, int n, int h, int w, int shave, int channel, float* out,
+                   void* scratch, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ AdamW (trainer.py:33-38, torch defaults)
  * One fused step over a flat float parameter arena: g' = g*grad_scale (1/world_size after a SUM all-reduce);
  * p *= 1 - lr*wd; m, v updated; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  `step_counter` is a DEVICE float
