@@ -121,6 +121,9 @@ SIGNATURES = {
     "fsr_loss_scale_update": (c_int, [P, c_float, c_float, c_float, P]),
     "fsr_adamw_step_ex": (c_int, [P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, P, c_float, P, c_float, P]),
     "fsr_crop_resize": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P]),
+    "fsr_crop_resize_aug": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, P]),
+    "fsr_dihedral_members": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "fsr_dihedral_accumulate": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P]),
     "fsr_copy_rows": (c_int, [P, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_degrade_blur_noise": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "fsr_jpeg_roundtrip": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P]),

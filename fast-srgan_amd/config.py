@@ -16,6 +16,11 @@ degradation of the LR batches on the device.  The keys are NOT in configs/config
 have no entry in DEFAULTS: train.make_degradation reads them with defaults of "off", and an override of a key the file lacks
 (`data.degradation.jpeg_prob=0.7`, `data.degradation.jpeg_quality=[30,95]`) creates the groups on its way.
 
+`data.augment.dihedral` (default false): random flips and 90-degree rotations of the training crops on the device, one of
+the 8 transform codes per sample.  An extension key of the same kind: not in configs/config.yaml or DEFAULTS, read by
+train.make_augmentation for the pre-training and training loaders (never the validation loader); any other `data.augment.*` key is an
+error.
+
 `training.lr_schedule.{kind, warmup, milestones, gamma, min_lr}`, `training.ema_decay`, `training.save_state` and `training.resume`
 (learning-rate schedules and a generator EMA that work under hipGraph replay, bit-exact resume) are extension keys of
 the same kind: absent from configs/config.yaml and DEFAULTS, read by the Trainer with defaults of "off".  `training.resume=auto` looks

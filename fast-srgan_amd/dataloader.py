@@ -113,6 +113,26 @@ class Degradation:
         return lr
 
 
+class Augmentation:
+    """Random flips and 90-degree rotations of the training crops on the device: with dihedral=True every sample gets
+    one of the 8 transform codes of ops.DIHEDRAL_INVERSE's table, drawn uniformly, and hr / lr are cut from D_k(crop)
+    (fsr_crop_resize_aug).  The draws come from this object's OWN random.Random: the index, crop and degradation streams of
+    DeviceBatchLoader do not move when it is switched on."""
+
+    def __init__(self, dihedral=True, seed=0):
+        self.dihedral = bool(dihedral)
+        self.seed = seed
+        self.rng = random.Random(seed)
+
+    @property
+    def enabled(self):
+        return self.dihedral
+
+    def draw(self, n):
+        """The transform codes of a batch of n samples."""
+        return [self.rng.randrange(8) for _ in range(n)]
+
+
 class NumpyImagesDataset(torch.utils.data.Dataset):
     def __init__(self, numpy_paths, lr_image_size, scale_factor, device="cuda"):
         self.numpy_paths = list(numpy_paths)
@@ -144,23 +164,33 @@ class NumpyImagesDataset(torch.utils.data.Dataset):
         _, h, w = self._image(idx).shape
         return rng.randint(0, h - self.hr_image_size), rng.randint(0, w - self.hr_image_size)
 
-    def batch(self, indices, crops, degrade=None):
+    def batch(self, indices, crops, degrade=None, xforms=None):
         """(lr, hr) float32 NCHW device batches for image `indices` cropped at `crops` [(y, x), ...].
         The per-sample descriptors (image pointer, height, width, crop origin) travel as ONE pinned, non-blocking
         host-to-device copy; nothing here waits for the device.
         degrade: a (Degradation, parameters it drew for this batch) pair -- lr then goes through its stages; the parameter
-        words ride at the end of the same copy."""
+        words ride at the end of the same copy.
+        xforms: one transform code 0..7 per sample -- hr and lr are then cut from D_k(crop) by fsr_crop_resize_aug, the
+        codes riding in the same copy, and the degradation runs on that lr; None: fsr_crop_resize, as ever."""
         n = len(indices)
         imgs = [self._image(i) for i in indices]
-        # [n int64 pointers][4 x n int32: heights, widths, crop_y, crop_x][degradation words]  (viewed as int64 words for one copy)
+        if xforms is not None:
+            xforms = [int(k) for k in xforms]
+            if len(xforms) != n or any(not 0 <= k <= 7 for k in xforms):
+                raise ValueError("batch: xforms must hold one transform code in 0..7 per sample, got %r" % (xforms,))
+        # [n int64 pointers][4 x n int32: heights, widths, crop_y, crop_x][n int32 transform codes, padded to an even count]
+        # [degradation words]  (viewed as int64 words for one copy)
         words = degrade[0].words(degrade[1]) if degrade is not None else None
         extra = 0 if words is None else words.size // 2              # ops.DEGRADE_WORDS is even
-        desc = np.empty(3 * n + extra, dtype=np.int64)
+        xw = 0 if xforms is None else (n + 1) // 2
+        desc = np.empty(3 * n + xw + extra, dtype=np.int64)
         desc[:n] = [im.data_ptr() for im in imgs]
         desc[n:3 * n].view(np.int32)[:] = ([im.shape[1] for im in imgs] + [im.shape[2] for im in imgs]
                                            + [c[0] for c in crops] + [c[1] for c in crops])
+        if xw:
+            desc[3 * n:3 * n + xw].view(np.int32)[:] = xforms + [0] * (2 * xw - n)
         if extra:
-            desc[3 * n:].view(np.int32)[:] = words
+            desc[3 * n + xw:].view(np.int32)[:] = words
         host = torch.from_numpy(desc)
         if self.device.type == "cuda":
             host = host.pin_memory()
@@ -170,11 +200,17 @@ class NumpyImagesDataset(torch.utils.data.Dataset):
         hr_out = torch.empty((n, 3, hr, hr), dtype=torch.float32, device=self.device)
         lr_out = torch.empty((n, 3, lr, lr), dtype=torch.float32, device=self.device)
         tmp = torch.empty((n, 3, hr, lr), dtype=torch.float32, device=self.device)
-        L.check(L.lib().fsr_crop_resize(_p(dev_desc), _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(meta[3]), n, hr,
-                                        self.scale_factor, _p(self._w), _p(self._xmin), _p(self._xsize), self._kmax,
-                                        _p(hr_out), _p(lr_out), _p(tmp), _stream()), "fsr_crop_resize")
+        if xforms is None:
+            L.check(L.lib().fsr_crop_resize(_p(dev_desc), _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(meta[3]), n, hr,
+                                            self.scale_factor, _p(self._w), _p(self._xmin), _p(self._xsize), self._kmax,
+                                            _p(hr_out), _p(lr_out), _p(tmp), _stream()), "fsr_crop_resize")
+        else:
+            codes = dev_desc[3 * n:3 * n + xw].view(torch.int32)
+            L.check(L.lib().fsr_crop_resize_aug(_p(dev_desc), _p(meta[0]), _p(meta[1]), _p(meta[2]), _p(meta[3]), _p(codes), n, hr,
+                                                self.scale_factor, _p(self._w), _p(self._xmin), _p(self._xsize), self._kmax,
+                                                _p(hr_out), _p(lr_out), _p(tmp), _stream()), "fsr_crop_resize_aug")
         if degrade is not None:
-            lr_out = degrade[0].apply(lr_out, degrade[1], dev_desc[3 * n:].view(torch.int32))
+            lr_out = degrade[0].apply(lr_out, degrade[1], dev_desc[3 * n + xw:].view(torch.int32))
         return lr_out, hr_out
 
     def __getitem__(self, idx):
@@ -190,13 +226,16 @@ class DeviceBatchLoader:
     python's RNG per worker).  sequential=True (validation, train.py:81-91: shuffle=False, drop_last=True): ONE pass over
     the data set in order, len(dataset) // batch_size batches, fresh random crops.  Under data parallelism each rank
     passes seed + rank.  degradation: a Degradation (with its own seed) applied to every lr batch; None, or one whose
-    probabilities are all 0, leaves every batch and every launch as it is.
+    probabilities are all 0, leaves every batch and every launch as it is.  augmentation: an Augmentation (with its own seed) whose
+    codes transform every crop before the down-scale and the degradation; None, or one with nothing switched on, likewise changes
+    nothing -- the state dictionary included, which gains its "augmentation" entry only when one is set.
     state_dict() / load_state_dict(): the three random streams and the batches already yielded -- a restored loader yields the
     REMAINING batches of the interrupted pass, the very ones the uninterrupted loader would have, and then stops."""
 
-    def __init__(self, dataset, batch_size, iterations=None, seed=1234, sequential=False, degradation=None):
+    def __init__(self, dataset, batch_size, iterations=None, seed=1234, sequential=False, degradation=None, augmentation=None):
         self.dataset, self.batch_size, self.sequential = dataset, batch_size, sequential
         self.degradation = degradation if degradation is not None and degradation.enabled else None
+        self.augmentation = augmentation if augmentation is not None and augmentation.enabled else None
         self.iterations = len(dataset) // batch_size if sequential else iterations
         if self.iterations is None:
             raise ValueError("DeviceBatchLoader needs `iterations` unless sequential=True")
@@ -214,15 +253,23 @@ class DeviceBatchLoader:
         return self.iterations
 
     def state_dict(self):
-        return {"generator": self.gen.get_state(), "rng": self.rng.getstate(), "yielded": self._yielded,
-                "degradation": None if self.degradation is None else self.degradation.rng.getstate()}
+        sd = {"generator": self.gen.get_state(), "rng": self.rng.getstate(), "yielded": self._yielded,
+              "degradation": None if self.degradation is None else self.degradation.rng.getstate()}
+        if self.augmentation is not None:
+            sd["augmentation"] = self.augmentation.rng.getstate()
+        return sd
 
     def load_state_dict(self, sd):
         if (sd["degradation"] is None) != (self.degradation is None):
             raise ValueError("DeviceBatchLoader.load_state_dict: the state was saved %s a degradation, this loader runs %s one"
                              % (("without", "with") if sd["degradation"] is None else ("with", "without")))
+        if (sd.get("augmentation") is None) != (self.augmentation is None):
+            raise ValueError("DeviceBatchLoader.load_state_dict: the state was saved %s an augmentation, this loader runs %s one"
+                             % (("without", "with") if sd.get("augmentation") is None else ("with", "without")))
         self.gen.set_state(sd["generator"])
         self.rng.setstate(sd["rng"])
+        if self.augmentation is not None:
+            self.augmentation.rng.setstate(sd["augmentation"])
         if self.degradation is not None:
             self.degradation.rng.setstate(sd["degradation"])
         self._yielded = int(sd["yielded"])
@@ -237,7 +284,10 @@ class DeviceBatchLoader:
             else:
                 idx = torch.randint(len(self.dataset), (self.batch_size,), generator=self.gen).tolist()
             crops = [self.dataset.draw_crop(i, self.rng) for i in idx]
-            if self.degradation is None:
+            degrade = None if self.degradation is None else (self.degradation, self.degradation.draw(len(idx)))
+            if self.augmentation is not None:
+                yield self.dataset.batch(idx, crops, degrade, self.augmentation.draw(len(idx)))
+            elif degrade is None:
                 yield self.dataset.batch(idx, crops)
             else:
-                yield self.dataset.batch(idx, crops, (self.degradation, self.degradation.draw(len(idx))))
+                yield self.dataset.batch(idx, crops, degrade)

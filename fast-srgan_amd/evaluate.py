@@ -14,6 +14,8 @@ one (N, 2) float32 copy per batch reaches the host, which finishes in float64:
 Without `--lr_dir` the LR images are made on the device by the training contract -- the dataloader's antialiased bicubic
 (ops.resample_image) of the mod-cropped HR image, quantised with rint and a clamp -- once per image, cached in the Evaluator.
 Evaluation runs eagerly (no graph capture: it happens once per checkpoint).
+`--self_ensemble` adds, beside every model's column, a column `<path>+` of its self-ensemble result (Generator.forward_u8 with
+ensemble=True): the EDSR+ / RCAN+ convention of the same tables.
 """
 import json
 import math
@@ -40,6 +42,8 @@ parser.add_argument("--baseline", action="store_true", help="add a column for an
 parser.add_argument("--batch", default=8, type=int, help="images of one shape per device batch")
 parser.add_argument("--bands", default="auto", choices=["auto", "on", "off"], help="as inference.py: the generator's tail in row bands")
 parser.add_argument("--band_rows", default=128, type=int)
+parser.add_argument("--self_ensemble", action="store_true",
+                    help="add a column <path>+ per model: the mean over the 8 flipped / transposed inputs (8x the generator work)")
 parser.add_argument("--json", default=None, type=str, help="write the settings, the per-image rows and the means here")
 parser.add_argument("--save_dir", default=None, type=str, help="write the super-resolved PNGs here (one sub-directory per model if several)")
 
@@ -132,22 +136,24 @@ class Evaluator:
                     b.lr = torch.cat([bicubic_u8(b.hr[j:j + 1], b.H // s, b.W // s) for j in range(len(items))])
             self.buckets.append(b)
 
-    def _limits(self, model, bands, band_rows):
+    def _limits(self, model, bands, band_rows, ensemble=False):
         """(h, w) -> (images per batch, rows per band or None) by InferencePipeline's rules."""
         if not hasattr(model, "max_batch"):
             return lambda h, w: (self.batch, None)
         from .inference import InferencePipeline
-        pipe = InferencePipeline(model, self.device, batch=self.batch, use_graph=False, bands=bands, band_rows=band_rows)
+        pipe = InferencePipeline(model, self.device, batch=self.batch, use_graph=False, bands=bands, band_rows=band_rows, ensemble=ensemble)
         return lambda h, w: (pipe._batch_for(h, w), pipe._bands_for(h, w))
 
     @torch.no_grad()
-    def run(self, model, bands="auto", band_rows=128, save_dir=None):
+    def run(self, model, bands="auto", band_rows=128, save_dir=None, ensemble=False):
         """{"images": [{"name", "psnr", "ssim"} in hr_paths' order], "psnr": mean, "ssim": mean} of `model` (anything with
-        Generator.forward_u8's signature).  save_dir: also write the super-resolved images there as PNGs."""
+        Generator.forward_u8's signature).  save_dir: also write the super-resolved images there as PNGs.  ensemble: score the
+        model's self-ensemble frames (forward_u8(..., ensemble=True); the argument is passed only when set)."""
         was_training = bool(getattr(model, "training", False))
         if hasattr(model, "eval"):
             model.eval()
-        limits = self._limits(model, bands, band_rows)
+        limits = self._limits(model, bands, band_rows, ensemble)
+        extra = {"ensemble": True} if ensemble else {}
         channels = ops.QUALITY_CHANNELS[self.channel][1]
         rows = [None] * len(self.paths)
         try:
@@ -155,7 +161,7 @@ class Evaluator:
                 n, rows_per_band = limits(b.lr.shape[1], b.lr.shape[2])
                 eh, ew = b.H - 2 * self.shave, b.W - 2 * self.shave
                 for j in range(0, len(b.index), n):
-                    sr = model.forward_u8(b.lr[j:j + n], bands=rows_per_band)
+                    sr = model.forward_u8(b.lr[j:j + n], bands=rows_per_band, **extra)
                     if tuple(sr.shape[1:]) != (b.H, b.W, 3):
                         raise ValueError("the model turned %s LR images into %s, expected %dx%d: is its scale %d?"
                                          % (tuple(b.lr.shape[1:3]), tuple(sr.shape[1:3]), b.H, b.W, self.scale))
@@ -227,12 +233,15 @@ def main(argv=None):
         if save is not None and len(args.model) > 1:
             save = os.path.join(save, os.path.splitext(os.path.basename(path))[0])
         columns.append(dict(ev.run(model, args.bands, args.band_rows, save), name=path))
+        if args.self_ensemble:
+            columns.append(dict(ev.run(model, args.bands, args.band_rows, None if save is None else save + "+", ensemble=True),
+                                name=path + "+"))
         del model
     print(format_table(ev.names, columns))
     if args.json:
         settings = {"hr_dir": args.hr_dir, "lr_dir": args.lr_dir, "scale": scale, "shave": ev.shave, "channel": ev.channel,
                     "compute_dtype": args.compute_dtype or getattr(config.training, "compute_dtype", "f16"), "batch": args.batch,
-                    "bands": args.bands, "band_rows": args.band_rows}
+                    "bands": args.bands, "band_rows": args.band_rows, "self_ensemble": bool(args.self_ensemble)}
         with open(args.json, "w") as f:
             json.dump({"settings": settings, "columns": columns}, f, indent=1)
     return columns

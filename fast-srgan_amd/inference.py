@@ -27,6 +27,8 @@ parser.add_argument("--bands", default="auto", choices=["auto", "on", "off"],
                     help="extension: run the generator's tail in row bands -- auto: for frames too large otherwise (above 1080p); on: whenever "
                          "that allows a larger batch; off: never")
 parser.add_argument("--band_rows", default=128, type=int, help="extension: core rows per band")
+parser.add_argument("--self_ensemble", action="store_true",
+                    help="extension: the self-ensemble (\"+\") result -- the mean over the 8 flipped / transposed inputs, 8x the generator work")
 _size_flags = parser.add_mutually_exclusive_group()
 _size_flags.add_argument("--size", default=None, type=str, metavar="WxH", help="extension: exact output size (default: 4x the input)")
 _size_flags.add_argument("--scale", default=None, type=float, help="extension: output size relative to the INPUT, e.g. 2 or 1.5")
@@ -94,9 +96,13 @@ class InferencePipeline:
     native plan, so both coexist; None or the native size IS the native plan.
     Row bands: bands="auto" runs the generator's tail in bands of `band_rows` core rows for the shapes that cannot run
     otherwise (max_batch(h, w) == 0: above 1080p for the shipped model), "on" for every shape whose batch that enlarges, "off" (the
-    default) never.  The frames are the same bytes; banded plans append ("bands", band_rows) to their key."""
+    default) never.  The frames are the same bytes; banded plans append ("bands", band_rows) to their key.
+    Self-ensemble (DESIGN.md §6j): ensemble=True makes `run` and `run_mixed` yield Generator.forward_u8(..., ensemble=True)'s frames;
+    such plans append ("ensemble",) to their key and hold a quarter of the frames per batch (`_member_limit`).  The YUV methods do not
+    take it."""
 
-    def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4, bands="off", band_rows=128):
+    def __init__(self, model, device="cuda", batch=8, depth=2, use_graph=True, copy=True, max_shapes=4, bands="off", band_rows=128,
+                 ensemble=False):
         """copy=False: `run` yields VIEWS of the pinned result buffers (valid until `depth` more batches have been
         submitted) instead of private arrays -- for consumers that encode / display a frame right away.
         max_shapes: plans (pinned staging, device buffers, captured graphs with their private pools) are kept for the
@@ -109,6 +115,7 @@ class InferencePipeline:
         if isinstance(band_rows, bool) or int(band_rows) != band_rows or band_rows < 1:
             raise ValueError("band_rows must be a positive integer, got %r" % (band_rows,))
         self.bands, self.band_rows = bands, int(band_rows)
+        self.ensemble = bool(ensemble)
         self.max_shapes = max(1, int(max_shapes))
         self._plans = {}            # (h, w) -> list of `depth` slots, built lazily (a one-batch bucket only ever builds slot 0)
         self._lru = []              # shapes, least recently used first
@@ -121,7 +128,7 @@ class InferencePipeline:
         that is too large on its own is refused here, before anything is allocated."""
         limit = self.model.max_batch(h, w) if hasattr(self.model, "max_batch") else self.batch
         if self._bands_for(h, w, limit) is not None:
-            limit = self.model.max_batch(h, w, bands=True)
+            limit = self._member_limit(self.model.max_batch(h, w, bands=True))
             if limit < 1:
                 px = self.model.max_batch(1, 1, bands=True)
                 raise ValueError("frames of %dx%d are too large: even with the tail in row bands a frame's largest activation would hold "
@@ -136,12 +143,19 @@ class InferencePipeline:
         if limit < 1:
             raise ValueError("frames of %dx%d are too large: one frame's largest activation would hold 2^31 or more elements, the limit "
                              "of the convolution kernels (max_batch = 0; 1920x1080 is the largest 16:9 input)" % (w, h))
+        limit = self._member_limit(limit)
         b = min(self.batch, limit)
         if b < self.batch and (h, w) not in self._told:
             self._told.add((h, w))
             print("InferencePipeline: %dx%d frames run in batches of %d instead of %d (the kernels index tensors below 2^31 elements)"
                   % (w, h, b, self.batch), file=sys.stderr)
         return b
+
+    def _member_limit(self, limit):
+        """The frame limit of a self-ensemble plan: a forward there runs the 4 members of an orientation group of every frame as one
+        batch, so a quarter of the kernels' limit keeps the groups whole.  Below 4 the limit stays -- forward_u8 then
+        runs the members in chunks, which changes no byte."""
+        return limit // 4 if self.ensemble and limit >= 4 else limit
 
     def _bands_for(self, h, w, whole=None):
         """Core rows per band for h x w inputs, or None when the shape runs whole: "auto" bands a shape that cannot run otherwise,
@@ -281,6 +295,8 @@ class InferencePipeline:
         pair but (8, 8), ("chroma", chroma, out_chroma) for any pair but ("420", "420"), ("layout", layout, out_layout) for any pair but
         ("planar", "planar") and ("bands", band_rows) for a banded plan.
         layout / out_layout ("planar" or "nv12"; out_layout defaults to layout): semi-planar 4:2:0 payloads in / out."""
+        if self.ensemble:
+            raise ValueError("InferencePipeline(ensemble=True) serves RGB frames only (run, run_mixed): the YUV paths have no self-ensemble")
         out_chroma = chroma if out_chroma is None else out_chroma
         out_layout = layout if out_layout is None else out_layout
         layout_code(layout, chroma)
@@ -327,7 +343,11 @@ class InferencePipeline:
             size = self._out_size(h, w, out_size)
             batch, rows = self._batch_for(h, w), self._bands_for(h, w)
             key = (h, w) if size is None else (h, w, "size") + size
-            if rows is not None:
+            if self.ensemble:       # self-ensemble plans append ("ensemble",): both kinds coexist
+                key += ("ensemble",) if rows is None else ("ensemble", "bands", rows)
+                fmt = self._Format(key, (h, w, 3),
+                                   lambda x, m=self.model, sz=size, r=rows: m.forward_u8(x, out_size=sz, bands=r, ensemble=True), batch)
+            elif rows is not None:
                 fmt = self._Format(key + ("bands", rows), (h, w, 3),
                                    lambda x, m=self.model, sz=size, r=rows: m.forward_u8(x, out_size=sz, bands=r), batch)
             elif size is None:
@@ -392,7 +412,7 @@ def main(argv=None):
                          if x.lower().endswith(".png") or x.lower().endswith(".jpg") or x.lower().endswith("jpeg"))
     print(f"Found {len(image_paths)} to super resolve, starting...")
     # (reports a batch it has to reduce for large frames, and a size it runs in row bands, once per size)
-    pipe = InferencePipeline(model, device, batch=args.batch, bands=args.bands, band_rows=args.band_rows)
+    pipe = InferencePipeline(model, device, batch=args.batch, bands=args.bands, band_rows=args.band_rows, ensemble=args.self_ensemble)
     resolve_out_size(1, 1, args.size, args.scale)      # a malformed --size fails before any image is read
 
     def load(name):

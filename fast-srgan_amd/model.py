@@ -93,7 +93,7 @@ class Generator(torch.nn.Module):
             raise ValueError("out_size must be (out_h, out_w) of positive integers, got %r" % (out_size,))
         return (int(oh), int(ow)) == (s * h, s * w)
 
-    def forward_u8(self, frames, out_size=None, bands=None):
+    def forward_u8(self, frames, out_size=None, bands=None, ensemble=False):
         """Inference on raw frames (inference.py:47-57 without the host round trips): (N,H,W,3) uint8 in, (N,4H,4W,3) uint8
         out.  The [-1,1] mapping (:48) is one small kernel in front of the neck; the head's epilogue applies :53-56
         ((y+1)/2 * 255, truncating cast) and stores bytes -- a 720p frame leaves the device as 2.8 MB instead of 11 MB of
@@ -102,8 +102,14 @@ class Generator(torch.nn.Module):
         antialiased bicubic resize with the same truncating cast (ops.resample_image).  None or the native size:
         the head's own epilogue, as before.
         bands = R: the tail runs in row bands of R core rows (`_tail_banded`): the same bytes, and batches up to
-        max_batch(h, w, bands=True)."""
+        max_batch(h, w, bands=True).
+        ensemble = True: the self-ensemble ("+") frames -- the mean of the float head outputs of the 8 flipped / transposed inputs,
+        each brought back to the frame's orientation, through the same cast (`_ensemble`)."""
         with torch.no_grad():
+            if ensemble:
+                native = self._native_size(frames.shape[1], frames.shape[2], out_size)
+                mean = self._ensemble(frames, "u8" if native else "f32", bands)
+                return mean if native else ops.resample_image(mean.permute(0, 2, 3, 1), int(out_size[0]), int(out_size[1]), "u8")
             if self._native_size(frames.shape[1], frames.shape[2], out_size):
                 return self._forward(ops.u8_to_image(frames), self._cfg_head_u8, bands)
             t = self._forward(ops.u8_to_image(frames), self._cfg_head, bands)
@@ -181,9 +187,36 @@ class Generator(torch.nn.Module):
         return self.forward_yuv(frames, h, w, "420", "420", siting, matrix, full_range, out_matrix, out_full_range, out_size, depth, out_depth,
                                 bands)
 
-    def forward(self, x, bands=None):
-        """bands = R (inference only: raises while gradients are enabled): the tail in row bands of R core rows."""
+    def forward(self, x, bands=None, ensemble=False):
+        """bands = R (inference only: raises while gradients are enabled): the tail in row bands of R core rows.
+        ensemble = True (inference only, likewise): the self-ensemble mean of the 8 members' float outputs."""
+        if ensemble:
+            return self._ensemble(x.permute(0, 2, 3, 1).contiguous(), "f32", bands)
         return self._forward(x, self._cfg_head, bands)
+
+    def _ensemble(self, frames, kind, bands=None):
+        """Self-ensemble of (N,H,W,3) frames, uint8 or float32 NHWC in [-1,1]: per orientation group (codes 0..3 keep
+        H x W, codes 4..7 are W x H) one member-input launch (ops.dihedral_members), the float head on the 4N members -- in chunks of
+        whole members when 4N exceeds max_batch; InstanceNorm statistics are per image, so the chunking changes no bit -- and one
+        accumulate launch per chunk (ops.dihedral_accumulate), which adds the outputs through the inverse transforms in code order.
+        kind "u8": uint8 (N,sH,sW,3); "f32": the float32 (N,3,sH,sW) view of an NHWC buffer."""
+        if torch.is_grad_enabled():
+            raise L.FsrError("ensemble: self-ensemble inference has no gradient; call it under torch.no_grad()")
+        n, h, w, _ = frames.shape
+        s = 2 ** len(self.upsampling)
+        per = min(4, self.max_batch(h, w, bands is not None) // n)      # members per forward (max_batch is symmetric in h and w)
+        if per < 1:
+            raise ValueError("ensemble: a batch of %d frames of %dx%d is too large for the convolution kernels (max_batch = %d)"
+                             % (n, w, h, self.max_batch(h, w, bands is not None)))
+        acc = torch.empty((n, s * h, s * w, 3), dtype=torch.float32, device=frames.device)
+        out = None
+        for g0 in (0, 4):
+            x = ops.dihedral_members(frames, g0, g0 + 3)
+            for k0 in range(g0, g0 + 4, per):
+                k1 = min(k0 + per, g0 + 4) - 1
+                y = self._forward(x[(k0 - g0) * n:(k1 - g0 + 1) * n], self._cfg_head, bands)
+                out = ops.dihedral_accumulate(y.permute(0, 2, 3, 1), k0, k1, acc, kind)
+        return out
 
     def _forward(self, x, cfg_head, bands=None):
         m = self._body(x)

@@ -1154,6 +1154,76 @@ def u8_to_image(frames):
     return img.permute(0, 3, 1, 2)
 
 
+# ---------------------------------------------------------------------------------- the eight symmetries of the rectangle
+DIHEDRAL_INVERSE = (0, 1, 2, 3, 4, 6, 5, 7)      # D_inv[k](D_k(x)) == x: codes 5 and 6 are each other's inverse
+ENSEMBLE_KINDS = {"f32": L.OUT_F32, "u8": L.OUT_U8}
+PROFILE_DIHEDRAL = None   # a list: every dihedral launch appends (what, start event, end event) -- tools/ensemble_bench.py
+
+
+def _check_codes(k0, k1, who):
+    for k in (k0, k1):
+        if isinstance(k, bool) or int(k) != k or not 0 <= k <= 7:
+            raise ValueError("%s: a transform code is an integer in 0..7, got %r" % (who, k))
+    if k0 > k1 or (k0 >> 2) != (k1 >> 2):
+        raise ValueError("%s: codes k0..k1 must lie in one orientation group (0..3 or 4..7), got %d..%d" % (who, k0, k1))
+    return int(k0), int(k1)
+
+
+def _profiled_dihedral(what, call):
+    prof = PROFILE_DIHEDRAL
+    if prof is None:
+        return call()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    call()
+    ev1.record()
+    prof.append((what, ev0, ev1))
+
+
+def dihedral_members(frames, k0=0, k1=3):
+    """The self-ensemble inputs of members k0..k1 (one orientation group: codes 0..3 or 4..7) of (N,H,W,3) frames -- uint8, or the
+    contiguous float32 NHWC buffer behind u8_to_image's view.  Returns the float32 ((k1-k0+1) N, 3, H, W) VIEW of an NHWC buffer for
+    codes 0..3, (..., 3, W, H) for codes 4..7, member-major: image (k - k0) N + i is D_k of frame i, and for uint8 frames equals
+    D_k(u8_to_image(frames)) bit for bit (fsr_dihedral_members)."""
+    _check_dev(frames)
+    k0, k1 = _check_codes(k0, k1, "dihedral_members")
+    if frames.dtype not in (torch.uint8, torch.float32) or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise ValueError("dihedral_members expects a contiguous (N,H,W,3) uint8 or float32 tensor, got %s %s" % (frames.dtype, tuple(frames.shape)))
+    n, h, w, _ = frames.shape
+    oh, ow = (h, w) if k0 < 4 else (w, h)
+    out = torch.empty(((k1 - k0 + 1) * n, oh, ow, 3), dtype=torch.float32, device=frames.device)
+    _profiled_dihedral("members", lambda: L.check(L.lib().fsr_dihedral_members(
+        _p(frames), int(frames.dtype == torch.uint8), n, h, w, k0, k1, _p(out), _stream()), "fsr_dihedral_members"))
+    return out.permute(0, 3, 1, 2)
+
+
+def dihedral_accumulate(y_nhwc, k0, k1, acc, kind="f32"):
+    """Adds the float head outputs of members k0..k1 onto the self-ensemble sum (fsr_dihedral_accumulate).  y_nhwc: contiguous float32
+    ((k1-k0+1) N, OH, OW, 3) for codes 0..3, (..., OW, OH, 3) for codes 4..7, member-major; acc: contiguous float32 (N, OH, OW, 3), the
+    running sum -- assigned by the call with k0 == 0, continued by the others, in code order.  The call with k1 == 7 leaves acc alone
+    and returns the mean instead: kind "f32" the float32 (N,3,OH,OW) view of an NHWC buffer, 0.125 * sum; kind "u8" the uint8
+    (N,OH,OW,3) frames by the truncating cast of forward_u8.  Other calls return None."""
+    _check_dev(y_nhwc, acc)
+    k0, k1 = _check_codes(k0, k1, "dihedral_accumulate")
+    if kind not in ENSEMBLE_KINDS:
+        raise ValueError("dihedral_accumulate kind must be one of %s, got %r" % (sorted(ENSEMBLE_KINDS), kind))
+    if acc.dtype != torch.float32 or acc.dim() != 4 or acc.shape[3] != 3 or not acc.is_contiguous():
+        raise ValueError("dihedral_accumulate expects a contiguous float32 (N,OH,OW,3) accumulator, got %s %s" % (acc.dtype, tuple(acc.shape)))
+    n, oh, ow, _ = acc.shape
+    want = ((k1 - k0 + 1) * n,) + ((oh, ow) if k0 < 4 else (ow, oh)) + (3,)
+    if y_nhwc.dtype != torch.float32 or tuple(y_nhwc.shape) != want or not y_nhwc.is_contiguous():
+        raise ValueError("dihedral_accumulate: members %d..%d of a %s sum are a contiguous float32 %s tensor, got %s %s"
+                         % (k0, k1, tuple(acc.shape), want, y_nhwc.dtype, tuple(y_nhwc.shape)))
+    out = None
+    if k1 == 7:
+        out = torch.empty((n, oh, ow, 3), dtype=torch.float32 if kind == "f32" else torch.uint8, device=acc.device)
+    _profiled_dihedral("accumulate", lambda: L.check(L.lib().fsr_dihedral_accumulate(
+        _p(y_nhwc), n, oh, ow, k0, k1, _p(acc), None if out is None else _p(out), ENSEMBLE_KINDS[kind], _stream()), "fsr_dihedral_accumulate"))
+    if out is None:
+        return None
+    return out.permute(0, 3, 1, 2) if kind == "f32" else out
+
+
 # ---------------------------------------------------------------------------------- row bands of the generator's tail (DESIGN.md §6e)
 TAIL_HALO = 2        # rows of the last up-sampling convolution's input discarded at each window edge that is not the frame's
 

@@ -14,7 +14,7 @@ import torch
 
 from . import distributed as D
 from .config import enter_run_dir, hydra_run_settings, load_config
-from .dataloader import Degradation, DeviceBatchLoader, NumpyImagesDataset
+from .dataloader import Augmentation, Degradation, DeviceBatchLoader, NumpyImagesDataset
 from .trainer import Trainer
 
 
@@ -73,15 +73,33 @@ def make_degradation(config, seed_value):
     return deg if deg.enabled else None
 
 
+def make_augmentation(config, seed_value):
+    """The Augmentation of one training loader from data.augment.* (`dihedral`, default false); None when nothing is
+    switched on, so that such a run builds the loaders it always built."""
+    node = getattr(config.data, "augment", None)
+    keys = ("dihedral",)
+    given = {} if node is None else {k: v for k, v in vars(node).items() if v is not None}
+    unknown = sorted(set(given) - set(keys))
+    if unknown:
+        raise ValueError("unknown data.augment key(s) %s (known: %s)" % (unknown, ", ".join(keys)))
+    if not isinstance(given.get("dihedral", False), bool):
+        raise ValueError("data.augment.dihedral must be true or false, got %r" % (given["dihedral"],))
+    aug = Augmentation(dihedral=given.get("dihedral", False), seed=seed_value)
+    return aug if aug.enabled else None
+
+
 def build_loaders(config, dataset, rank=0):
-    """(validation, pre-training, training) loaders; seeds derive from experiment.seed and the rank, the degradations' too."""
+    """(validation, pre-training, training) loaders; seeds derive from experiment.seed and the rank, the degradations' and the
+    augmentations' too.  The validation loader is never augmented."""
     bs, base = config.training.batch_size, config.experiment.seed
     val = DeviceBatchLoader(dataset, bs, seed=base + 7919 * (rank + 1), sequential=True,                 # train.py:81-91
                             degradation=make_degradation(config, base + 15485863 * (rank + 1)))
     pre = DeviceBatchLoader(dataset, bs, config.training.pretrain_iterations, seed=base + rank,
-                            degradation=make_degradation(config, base + 32452843 * (rank + 1)))
+                            degradation=make_degradation(config, base + 32452843 * (rank + 1)),
+                            augmentation=make_augmentation(config, base + 67867967 * (rank + 1)))
     trn = DeviceBatchLoader(dataset, bs, config.training.iterations, seed=base + 104729 * (rank + 1),
-                            degradation=make_degradation(config, base + 49979687 * (rank + 1)))
+                            degradation=make_degradation(config, base + 49979687 * (rank + 1)),
+                            augmentation=make_augmentation(config, base + 86028121 * (rank + 1)))
     return val, pre, trn
 
 

@@ -492,6 +492,37 @@ int fsr_crop_resize(const uint8_t* const* images, const int* img_h, const int* i
                     const int* crop_x, int n, int hr_size, int scale, const float* wtab, const int* xmin,
                     const int* xsize, int kmax, float* hr_out, float* lr_out, float* tmp, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ the eight symmetries of the rectangle (added within ABI 16: new entry
+ * points only).  Code k in 0..7 acts on an H x W image in three steps: k & 1 flips the width axis, k & 2 flips the height
+ * axis, then k & 4 transposes H and W -- codes 4..7 produce a W x H image.  The inverse of D_k is "transpose first, then the flips": as a
+ * code, k itself except that 5 and 6 are each other's inverse.  Codes 0..3 and 4..7 are the two ORIENTATION GROUPS; one call serves
+ * codes k0..k1 of one group.
+ *
+ * fsr_dihedral_members (self-ensemble input): src is n images [n,h,w,3], uint8 (src_is_u8 != 0) or float; out receives the float images
+ * of members k0..k1, member-major: image (k - k0) n + i is D_k of image i, [h,w,3] for codes 0..3 and [w,h,3] for codes 4..7.  A uint8
+ * source is mapped by fsr_u8_to_image's expression x / 127.5 - 1, so a member is D_k(fsr_u8_to_image(x)) bit for bit; a float source is
+ * copied.
+ *
+ * fsr_dihedral_accumulate (self-ensemble output): y holds the float outputs of members k0..k1 in that layout, for a result of h x w
+ * ([n,h,w,3] each for codes 0..3, [n,w,h,3] for 4..7).  They are read through the inverse transforms and added in code order, in float32,
+ * onto the running sum: s = y_0 (k0 == 0; acc is not read) or acc (k0 > 0), then s = s + y_k' for the remaining codes of the call.  A
+ * call with k1 < 7 stores s to acc [n,h,w,3]; the call with k1 == 7 stores to `out` instead: out_kind FSR_OUT_F32 float [n,h,w,3] =
+ * 0.125f s (out may be acc), FSR_OUT_U8 uint8 [n,h,w,3] = (unsigned char)(clamp((0.125f s + 1) / 2, 0, 1) * 255), the truncating cast of
+ * fsr_resample_image's FSR_OUT_U8 and of fsr_conv3x3's.  The order of the sum is that of the codes whatever the split into calls.
+ *
+ * fsr_crop_resize_aug (training augmentation): fsr_crop_resize with a per-sample code xform [n] (device ints; only the low 3 bits are
+ * read): hr = D_k(crop) and lr = the down-scale of D_k(crop), pass 1 reading the source through D_k and everything behind it unchanged --
+ * the batch fsr_crop_resize cuts from a data set holding D_k(image).  Crops are square, so every code keeps the shapes.
+ *
+ * Refused with nothing launched: null pointers, non-positive n, h, w, n > 65535, codes outside 0..7, k0 > k1, a range that spans both
+ * groups, an unknown out_kind. */
+int fsr_dihedral_members(const void* src, int src_is_u8, int n, int h, int w, int k0, int k1, float* out, fsr_stream_t stream);
+int fsr_dihedral_accumulate(const float* y, int n, int h, int w, int k0, int k1, float* acc, void* out, int out_kind,
+                            fsr_stream_t stream);
+int fsr_crop_resize_aug(const uint8_t* const* images, const int* img_h, const int* img_w, const int* crop_y, const int* crop_x,
+                        const int* xform, int n, int hr_size, int scale, const float* wtab, const int* xmin, const int* xsize, int kmax,
+                        float* hr_out, float* lr_out, float* tmp, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ training degradations (added within ABI 16: new entry points only)
  * Both work on float NCHW batches [n,3,h,w] in [-1,1] (what fsr_crop_resize writes); every per-sample array is a DEVICE pointer.
  *
