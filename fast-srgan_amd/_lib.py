@@ -23,6 +23,7 @@ CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr
 LAYOUT_PLANAR, LAYOUT_NV12 = 0, 1                # payload layout of the fsr_*_yuv_ex entry points
 BLUR_MAX_RADIUS, BLUR_TAPS = 9, 19               # fsr_degrade_blur_noise
 QUALITY_Y, QUALITY_RGB = 0, 1                    # fsr_quality_u8
+LOSS_L1, LOSS_SMOOTH_L1, LOSS_CHARBONNIER, LOSS_MSE = 0, 1, 2, 3    # fsr_elem_loss_fwd / _bwd
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
 ABI_VERSION = 16
 
@@ -111,7 +112,10 @@ SIGNATURES = {
     "fsr_bce_logits_bwd": (c_int, [P, P, P, P, c_ll, P]),
     "fsr_smooth_l1_fwd": (c_int, [c_int, P, P, P, P, c_ll, P]),
     "fsr_smooth_l1_bwd": (c_int, [c_int, P, P, P, P, c_ll, P]),
-    "fsr_ssim_sse_scratch": (c_size_t, [c_int, c_int, c_int]),
+    "fsr_elem_loss_scratch": (c_size_t, []),
+    "fsr_elem_loss_fwd": (c_int, [c_int, c_float, P, c_ll, c_ll, c_ll, c_ll, P, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, P, P, P]),
+    "fsr_elem_loss_bwd": (c_int, [c_int, c_float, P, c_ll, c_ll, c_ll, c_ll, P, c_ll, c_ll, c_ll, c_ll, P, P, c_int, c_int, c_int, c_int, P]),
+    "fsr_ssim_sse_scratch":(c_size_t, [c_int, c_int, c_int]),
     "fsr_ssim_sse": (c_int, [P, c_ll, c_ll, c_ll, c_ll, P, c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_int, P, P, P]),
     "fsr_quality_u8_scratch": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "fsr_quality_u8": (c_int, [P, c_ll, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, P, P, P]),

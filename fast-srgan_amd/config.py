@@ -30,6 +30,10 @@ under `runs/<experiment.name>/` of the run directory, so it goes with `hydra.run
 by the benchmark protocol, logged at the checkpoints of the GAN phase) are extension keys of the same kind; train.main makes the
 directory absolute before the run directory is entered.
 
+`training.loss.{adversarial, content, pixel, pixel_kind, pixel_eps, gan, pretrain_kind}` (the weights of the generator's
+loss terms, an element-wise pixel term, a least-squares adversarial term) are extension keys of the same kind, read and validated by the
+Trainer with the reference's objective as defaults; any other `training.loss.*` key is an error.
+
 hydra run directory (/root/reference/train.py:46 is `@hydra.main(version_base="1.1", ...)`, under which hydra changes the
 working directory to `outputs/<date>/<time>` before `main` runs, so `runs/...` checkpoints land there): `enter_run_dir`
 reproduces that, including hydra's own override keys `hydra.run.dir=<path>` and `hydra.job.chdir=false`.

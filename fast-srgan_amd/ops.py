@@ -1084,6 +1084,58 @@ class SmoothL1Fn(torch.autograd.Function):
         return da, None, None
 
 
+ELEM_LOSS_KINDS = {"l1": L.LOSS_L1, "smooth_l1": L.LOSS_SMOOTH_L1, "charbonnier": L.LOSS_CHARBONNIER, "mse": L.LOSS_MSE}
+
+
+def _elem_loss_check(a, b, kind, eps):
+    """The operand and parameter checks of elem_loss; returns (kind code, eps as a float)."""
+    code = ELEM_LOSS_KINDS.get(kind)
+    if code is None:
+        raise ValueError("elem_loss: unknown kind %r (known: %s)" % (kind, ", ".join(ELEM_LOSS_KINDS)))
+    eps = float(eps)
+    if code == L.LOSS_CHARBONNIER and not (0.0 < eps < float("inf")):
+        raise ValueError("elem_loss: Charbonnier's eps must be positive and finite, got %r" % (eps,))
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise L.FsrError("elem_loss: operands must be float32 (the head stores and the loaders hand out float32), got %s and %s"
+                         % (a.dtype, b.dtype))
+    if a.dim() != 4 or a.shape != b.shape:
+        raise L.FsrError("elem_loss: operands must be two (N,C,H,W) tensors of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    if b.requires_grad:
+        raise L.FsrError("elem_loss: the second operand is the target and gets no gradient, but it requires one")
+    return code, eps
+
+
+class ElemLossFn(torch.autograd.Function):
+    """mean psi(a - b) over two float32 (N,C,H,W) tensors of ANY strides, psi by `code` (fsr_elem_loss_fwd / _bwd); b is the target."""
+
+    @staticmethod
+    def forward(ctx, a, b, code, eps):
+        _check_dev(a, b)
+        loss = _zeros((1,), a.device).view(())
+        scr = _workspace(L.lib().fsr_elem_loss_scratch(), a.device)
+        L.check(L.lib().fsr_elem_loss_fwd(code, eps, _p(a), *a.stride(), _p(b), *b.stride(), *a.shape, _p(loss), _p(scr), _stream()),
+                "fsr_elem_loss_fwd")
+        ctx.code, ctx.eps = code, eps
+        ctx.save_for_backward(a, b)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        g = g.contiguous().float()
+        da = torch.empty_strided(a.shape, a.stride(), dtype=torch.float32, device=a.device)
+        L.check(L.lib().fsr_elem_loss_bwd(ctx.code, ctx.eps, _p(a), *a.stride(), _p(b), *b.stride(), _p(g), _p(da), *a.shape, _stream()),
+                "fsr_elem_loss_bwd")
+        return da, None, None, None
+
+
+def elem_loss(a, b, kind="l1", eps=1e-3):
+    """Mean element-wise loss between float32 (N,C,H,W) tensors, each read through its own strides (no copies): kind = l1, smooth_l1
+    (beta 1), charbonnier (sqrt(d^2 + eps^2); 1e-3 is LapSRN's eps) or mse.  b is the target: it must not require a gradient."""
+    code, eps = _elem_loss_check(a, b, kind, eps)
+    return ElemLossFn.apply(a, b, code, eps)
+
+
 def bce_with_logits(x, t):
     return BCEWithLogitsFn.apply(x, t)
 

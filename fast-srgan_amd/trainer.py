@@ -16,6 +16,11 @@ optimizers of the GAN phase on a device-side learning-rate schedule (effective u
 exponential moving average of the generator (Trainer.generator_ema, generator_ema_epoch_N.pt), training.save_state adds
 state_N.pt to every checkpoint and training.resume=<state_N.pt | auto> continues such a run bit for bit.
 
+Training objective (extension keys, the reference's objective by default): training.loss.{adversarial,content,pixel} weigh
+the generator's terms through the backward seeds, training.loss.pixel_kind / pixel_eps choose the pixel term (ops.elem_loss on the
+generator's output and the HR batch, in place), training.loss.gan=lsgan replaces BCE by least squares on the logits,
+training.loss.pretrain_kind the loss of pretrain_step; training.loss.content=0 runs without the perceptual network.
+
 Benchmark evaluation (extension keys, off by default): training.eval_dir=<HR directory>, training.eval_shave and
 training.eval_channel log whole-image PSNR / SSIM by the benchmark protocol at the checkpoints of the GAN phase
 (GAN/Eval/PSNR_Y, GAN/Eval/SSIM_Y, and GAN/EMA/Eval/... for the EMA generator).
@@ -49,6 +54,40 @@ def _schedule_settings(config):
         return None
     given.setdefault("kind", "multistep" if "milestones" in given else "constant")
     return given
+
+
+_LOSS_DEFAULTS = {"adversarial": 0.05, "content": 0.5, "pixel": 0.0, "pixel_kind": "l1", "pixel_eps": 1e-3, "gan": "bce",
+                  "pretrain_kind": "smooth_l1"}
+_LOSS_WEIGHTS = ("adversarial", "content", "pixel")
+
+
+def _objective_settings(config):
+    """training.loss.*  as (objective, given): the settings with the reference's objective as defaults, and whether a
+    training.loss node was there at all.  Not in configs/config.yaml, like training.lr_schedule.*."""
+    node = getattr(config.training, "loss", None)
+    given = {} if node is None else {k: v for k, v in (node.items() if isinstance(node, dict) else vars(node).items()) if v is not None}
+    unknown = sorted(set(given) - set(_LOSS_DEFAULTS))
+    if unknown:
+        raise ValueError("unknown training.loss key(s) %s (known: %s)" % (unknown, ", ".join(_LOSS_DEFAULTS)))
+    obj = dict(_LOSS_DEFAULTS, **given)
+    for k in _LOSS_WEIGHTS + ("pixel_eps",):
+        try:
+            obj[k] = float(obj[k])
+        except (TypeError, ValueError):
+            raise ValueError("training.loss.%s must be a number, got %r" % (k, obj[k])) from None
+    for k in _LOSS_WEIGHTS:
+        if not 0.0 <= obj[k] < float("inf"):
+            raise ValueError("training.loss.%s must be finite and >= 0, got %r" % (k, obj[k]))
+    if not any(obj[k] > 0.0 for k in _LOSS_WEIGHTS):
+        raise ValueError("training.loss: adversarial, content and pixel are all 0 -- the generator would have no objective")
+    if not 0.0 < obj["pixel_eps"] < float("inf"):
+        raise ValueError("training.loss.pixel_eps must be positive and finite, got %r" % (obj["pixel_eps"],))
+    for k in ("pixel_kind", "pretrain_kind"):
+        if obj[k] not in ops.ELEM_LOSS_KINDS:
+            raise ValueError("training.loss.%s must be one of %s, got %r" % (k, ", ".join(ops.ELEM_LOSS_KINDS), obj[k]))
+    if obj["gan"] not in ("bce", "lsgan"):
+        raise ValueError("training.loss.gan must be bce or lsgan, got %r" % (obj["gan"],))
+    return obj, node is not None
 
 
 class _NullWriter:
@@ -85,18 +124,22 @@ class Trainer:
         cdt = getattr(config.training, "compute_dtype", "f16")
         self.is_main = D.rank() == 0
         self.writer = _make_writer(osp.join("runs", config.experiment.name)) if self.is_main else _NullWriter()
+        self.objective, self._objective_given = _objective_settings(config)     # training.loss.*: refused before anything is built
         self.generator = Generator(config=config.generator, compute_dtype=cdt).to(dev)
         self.discriminator = Discriminator(config=config.discriminator, compute_dtype=cdt).to(dev)
-        if perceptual_network is None:      # extension keys: training.vgg19_weights (path), training.allow_random_vgg
+        # training.loss.content=0: the perceptual branch is off -- no network is built (no VGG weights needed), a given one is kept
+        # but never called
+        if perceptual_network is None and self.objective["content"] > 0.0:      # extension keys: training.vgg19_weights (path), training.allow_random_vgg
             vgg_weights = vgg_weights or getattr(config.training, "vgg19_weights", None) or None
             perceptual_network = VGG19(weights=vgg_weights, compute_dtype=cdt,
                                        allow_random=bool(getattr(config.training, "allow_random_vgg", False)))
-        self.perceptual_network = perceptual_network.to(dev)
+        self.perceptual_network = perceptual_network.to(dev) if perceptual_network is not None else None
         # training.compiled (trainer.py:23-26) selects torch.compile/Triton in the reference; here every op is
         # already a hand-written HIP kernel, so the key is accepted and changes nothing.
-        self.perceptual_network.eval()
-        for p in self.perceptual_network.parameters():
-            p.requires_grad = False
+        if self.perceptual_network is not None:
+            self.perceptual_network.eval()
+            for p in self.perceptual_network.parameters():
+                p.requires_grad = False
         self._lr_schedule = _schedule_settings(config)
         if self._lr_schedule is not None:
             self._schedules()               # bad values are refused here, not when the GAN phase begins
@@ -129,7 +172,8 @@ class Trainer:
         # 2^20 .. 2^22 track fp32; 2^26 overflows, is halved four times in the first iterations and then tracks fp32 too.
         # (x3v: the perceptual network alone runs in fp16 -- its backward needs the scale all the same; the x3 networks share
         # float32's exponent range and are indifferent to it)
-        scaled = "f16" in (self.generator.compute.name, self.perceptual_network.compute.name)
+        scaled = "f16" in ((self.generator.compute.name, self.perceptual_network.compute.name) if self.objective["content"] > 0.0
+                           else (self.generator.compute.name,))
         self.loss_scale = float(getattr(config.training, "loss_scale", 1048576.0 if scaled else 1.0))
         if not (self.loss_scale > 0.0 and self.loss_scale == self.loss_scale and self.loss_scale != float("inf")):
             raise ValueError("training.loss_scale must be a positive finite number, got %r" % (self.loss_scale,))
@@ -169,7 +213,13 @@ class Trainer:
             self.generator_ema.eval()
             self.optim_generator.attach_ema_params(self.generator_ema.parameters())
         self.loss_fn = ops.bce_with_logits      # torch.nn.BCEWithLogitsLoss(), trainer.py:41
+        if self.objective["gan"] == "lsgan":    # least squares on the raw logits, same noisy labels and weights
+            self.loss_fn = lambda logits, labels: ops.elem_loss(logits, labels, "mse")
         self.l1_loss = ops.smooth_l1            # torch.nn.SmoothL1Loss(), trainer.py:43
+        # Backward-seed weights, in the order their seeds are made: the discriminator's 0.5 / 0.5 (trainer.py:179), then the
+        # generator's terms (the defaults are trainer.py:188,194's 0.5 * 1e-1 and 0.5); a term of weight 0 has no seed and is not computed
+        self._seed_weights = {"discriminator": 0.5}
+        self._seed_weights.update((k, self.objective[k]) for k in _LOSS_WEIGHTS if self.objective[k] > 0.0)
 
     def _side_stream(self, device):
         st = self._streams.get(str(device))
@@ -214,7 +264,9 @@ class Trainer:
         # fill the gaps the discriminator / generator kernels leave (tails, 1-workgroup-per-CU weight gradients,
         # bandwidth-bound elementwise passes).  Captured hipGraphs keep the two branches as parallel graph paths.
         main = torch.cuda.current_stream() if lr_images.is_cuda else None
-        side = self._side_stream(dev) if (main is not None and self.use_side_stream) else None
+        obj = self.objective
+        use_content = obj["content"] > 0.0      # off: nothing is queued on the side stream, so there is nothing to join either
+        side = self._side_stream(dev) if (main is not None and self.use_side_stream and use_content) else None
 
         def on_side(fn):
             """fn's launches go to the side stream, ordered after everything queued on the main stream SO FAR."""
@@ -228,12 +280,17 @@ class Trainer:
             with torch.no_grad():                                               # :191 (no gradient needed: target)
                 return V.features_nhwc(hr_images)
 
-        real_features = on_side(features_no_grad)
+        real_features = on_side(features_no_grad) if use_content else None
         self.optim_discriminator.zero_grad()                                    # :171
         sr_images = G(lr_images)                                                # :173 / :185 (shared)
         # content branch of the generator step (:190, :192): queued behind G(lr) only -- the side stream starts it as soon
         # as sr_images exists, beside the discriminator's forward and backward
-        content_loss = on_side(lambda: self.l1_loss(V.features_nhwc(sr_images), real_features, cd=V.compute))
+        if use_content:
+            content_loss = on_side(lambda: self.l1_loss(V.features_nhwc(sr_images), real_features, cd=V.compute))
+        else:
+            content_loss = ops._zeros((1,), dev).view(())       # an exact 0 from the iteration's zeroed arena: no launch
+        # the pixel term reads sr_images (the NCHW view of the head's NHWC buffer) and the loader's batch in place, through their strides
+        pixel_loss = ops.elem_loss(sr_images, hr_images, obj["pixel_kind"], obj["pixel_eps"]) if obj["pixel"] > 0.0 else None
         # :172 and :174 use the same discriminator weights and every op is per-sample, so real and fake images go
         # through D as ONE batch of 2B: half the launches, one weight-gradient pass instead of two
         y_both = Dm(torch.cat([hr_images, sr_images.detach()], dim=0))
@@ -246,15 +303,15 @@ class Trainer:
         loss_fake = self.loss_fn(y_fake, fake_labels)                           # :178
         # :179-180  backward of 0.5 * loss_real + 0.5 * loss_fake: the weights ride in the two backward seeds (times the loss
         # scale, if any) -- no scalar-arithmetic kernels and no Mul / Add nodes in the iteration
-        half = self._seeds(lr_images.device)[0]
+        half = self._seeds(lr_images.device)["discriminator"]
         torch.autograd.backward([loss_real, loss_fake], [half, half])
         ops.wgrad_stream_join()
         joined = False
         if join_side and side is not None:      # a captured phase must end with every forked stream joined
             main.wait_stream(side)
             joined = True
-        return dict(sr=sr_images, content=content_loss, loss_real=loss_real, loss_fake=loss_fake, main=main, side=side,
-                    joined=joined)
+        return dict(sr=sr_images, content=content_loss, pixel=pixel_loss, loss_real=loss_real, loss_fake=loss_fake, main=main,
+                    side=side, joined=joined)
 
     def _phase_g(self, st, noise):
         Dm = self.discriminator
@@ -263,16 +320,25 @@ class Trainer:
         self.optim_discriminator.step()                                         # :181
         for p in Dm.parameters():
             p.requires_grad_(False)      # D's weight gradients of this pass are discarded by the reference (:171)
+        terms = {}
         try:
-            y_fake = Dm(st["sr"])                                               # :186 (updated D)
-            real_labels = torch.empty_like(y_fake).uniform_(0.7, 1.0) if noise is None else 0.3 * noise[2] + 0.7   # :187
-            bce = self.loss_fn(y_fake, real_labels)
-            adv_loss = bce.detach() * 1e-1                                      # :188 (the reported value)
+            if "adversarial" in self._seed_weights:
+                y_fake = Dm(st["sr"])                                           # :186 (updated D)
+                real_labels = torch.empty_like(y_fake).uniform_(0.7, 1.0) if noise is None else 0.3 * noise[2] + 0.7   # :187
+                terms["adversarial"] = self.loss_fn(y_fake, real_labels)
+                adv_loss = terms["adversarial"].detach() * 1e-1                 # :188 (the reported value, whatever the weight)
+            else:                       # training.loss.adversarial=0: the generator does not see D at all
+                adv_loss = ops._zeros((1,), st["sr"].device).view(())
             if st["side"] is not None and not st["joined"]:
                 st["main"].wait_stream(st["side"])
-            # :194-195  backward of 0.5 * (0.1 * bce) + 0.5 * content_loss, the weights in the seeds as above
-            half, adv_w = self._seeds(y_fake.device)
-            torch.autograd.backward([bce, st["content"]], [adv_w, half])
+            # :194-195  backward of 0.5 * (0.1 * bce) + 0.5 * content_loss (+ pixel * pixel_loss), the weights in the seeds as above:
+            # ONE backward call, so the terms' gradients of sr_images are summed and G's backward runs once
+            if "content" in self._seed_weights:
+                terms["content"] = st["content"]
+            if "pixel" in self._seed_weights:
+                terms["pixel"] = st["pixel"]
+            seeds = self._seeds(st["sr"].device)
+            torch.autograd.backward(list(terms.values()), [seeds[k] for k in terms])
         finally:
             for p in Dm.parameters():
                 p.requires_grad_(True)
@@ -280,16 +346,24 @@ class Trainer:
         st["adv"] = adv_loss
 
     def _seeds(self, dev):
-        """(0.5 S, 0.05 S) as 0-dim device tensors, S = the loss scale (1 without one): the backward seeds that carry
-        trainer.py:179 / :188 / :194's loss weights.  Constant scales: made once (before any graph capture: the warm-up
-        iterations come first); the dynamic fp16 scale lives on the device, so its seeds are two tiny launches per phase."""
+        """{term: w S} as 0-dim device tensors, S = the loss scale (1 without one): the backward seeds that carry the loss weights
+        (trainer.py:179 / :188 / :194's 0.5 and 0.05 by default, training.loss.* otherwise), ONE tensor per distinct weight.
+        Constant scales: made once (before any graph capture: the warm-up iterations come first); the dynamic fp16 scale lives on
+        the device, so its seeds are one tiny launch per distinct weight and phase (two by default)."""
         if self._scale_state is not None:
-            return self._seed * 0.5, self._seed * 0.05
+            by_weight = {}
+            for w in self._seed_weights.values():
+                if w not in by_weight:
+                    by_weight[w] = self._seed * w
+            return {k: by_weight[w] for k, w in self._seed_weights.items()}
         c = self._seed_consts.get(str(dev))
         if c is None:
             s = 1.0 if self._seed is None else float(self.loss_scale)
-            c = self._seed_consts[str(dev)] = (torch.tensor(0.5 * s, dtype=torch.float32, device=dev),
-                                               torch.tensor(0.05 * s, dtype=torch.float32, device=dev))
+            by_weight = {}
+            for w in self._seed_weights.values():
+                if w not in by_weight:
+                    by_weight[w] = torch.tensor(w * s, dtype=torch.float32, device=dev)
+            c = self._seed_consts[str(dev)] = {k: by_weight[w] for k, w in self._seed_weights.items()}
         return c
 
     def _clear_nonfinite_flag(self):
@@ -314,8 +388,12 @@ class Trainer:
         self.optim_generator.step()                                             # :196
         self._update_loss_scale()
         # the loss scalars live in the per-iteration scratch arena: copy them out (one launch) so they survive the next reset
-        vals = torch.stack([st["loss_real"].detach(), st["loss_fake"].detach(), st["adv"].detach(), st["content"].detach()])
-        return dict(zip(("loss_real", "loss_fake", "adv_loss", "content_loss"), vals.unbind(0)))
+        keys = ["loss_real", "loss_fake", "adv_loss", "content_loss"]
+        vals = [st["loss_real"].detach(), st["loss_fake"].detach(), st["adv"].detach(), st["content"].detach()]
+        if st["pixel"] is not None:     # training.loss.pixel > 0: the unweighted mean
+            keys.append("pixel_loss")
+            vals.append(st["pixel"].detach())
+        return dict(zip(keys, torch.stack(vals).unbind(0)))
 
     # ------------------------------------------------------------------ hipGraph replay of the whole iteration
     def capture_train_step(self, lr_images, hr_images, warmup=2, noise=None):
@@ -415,7 +493,10 @@ class Trainer:
             self._clear_nonfinite_flag()
             self.optim_generator.zero_grad()
             fake_hr_images = self.generator(lr_images)
-            gen_loss = self.l1_loss(fake_hr_images, hr_images)
+            if self.objective["pretrain_kind"] == "smooth_l1":
+                gen_loss = self.l1_loss(fake_hr_images, hr_images)
+            else:
+                gen_loss = ops.elem_loss(fake_hr_images, hr_images, self.objective["pretrain_kind"], self.objective["pixel_eps"])
             gen_loss.backward(self._seed)
             self._sync_g.run()
             self.optim_generator.step()
@@ -559,9 +640,12 @@ class Trainer:
         if self.generator_ema is not None:
             torch.save(self.generator_ema.state_dict(), osp.join(save_dir, f"generator_ema_epoch_{step}.pt"))
         if self.save_state:
-            torch.save({"step": int(step), "generator": self.generator.state_dict(), "discriminator": self.discriminator.state_dict(),
-                        "optim_generator": self.optim_generator.state_dict(), "optim_discriminator": self.optim_discriminator.state_dict(),
-                        "rank_state": self._rank_state(train_dataloader, val_dataloader)}, osp.join(save_dir, f"state_{step}.pt"))
+            state = {"step": int(step), "generator": self.generator.state_dict(), "discriminator": self.discriminator.state_dict(),
+                     "optim_generator": self.optim_generator.state_dict(), "optim_discriminator": self.optim_discriminator.state_dict(),
+                     "rank_state": self._rank_state(train_dataloader, val_dataloader)}
+            if self._objective_given:       # training.loss.*: what the run optimised (a default run's file keeps its keys)
+                state["objective"] = dict(self.objective)
+            torch.save(state, osp.join(save_dir, f"state_{step}.pt"))
 
     # ------------------------------------------------------------------ training.save_state / training.resume
     def _rank_state(self, train_dataloader, val_dataloader):
@@ -609,6 +693,12 @@ class Trainer:
     def load_state(self, path, train_dataloader=None, val_dataloader=None):
         """Restores a state_N.pt (save_checkpoints with training.save_state); returns N, the step it was written after."""
         st = torch.load(path, map_location="cpu")
+        saved_objective = dict(_LOSS_DEFAULTS, **(st.get("objective") or {}))      # no entry: the default objective
+        if saved_objective != self.objective:
+            import warnings
+            changed = sorted(k for k in _LOSS_DEFAULTS if saved_objective.get(k) != self.objective[k])
+            warnings.warn("training.resume: %s was written under another training objective (%s); continuing with the configured one"
+                          % (path, ", ".join("%s: %r -> %r" % (k, saved_objective.get(k), self.objective[k]) for k in changed)))
         for what, opt, key in (("generator", self.optim_generator, "optim_generator"),
                                ("discriminator", self.optim_discriminator, "optim_discriminator")):
             saved = sum(int(v["exp_avg"].numel()) for v in st[key]["state"].values())
@@ -687,6 +777,8 @@ class Trainer:
                 self.writer.add_scalar("Loss/Discriminator/Fake", losses["loss_fake"], global_step=step)
                 self.writer.add_scalar("Loss/Generator/Adversarial", losses["adv_loss"], global_step=step)
                 self.writer.add_scalar("Loss/Generator/Content", losses["content_loss"], global_step=step)
+                if "pixel_loss" in losses:
+                    self.writer.add_scalar("Loss/Generator/Pixel", losses["pixel_loss"], global_step=step)
                 if self._lr_schedule is not None:
                     self.writer.add_scalar("Loss/LR", self.optim_generator.lr_used(), global_step=step)
             if step % self.config.training.checkpoint_iter == 0:

@@ -547,6 +547,28 @@ int fsr_degrade_blur_noise(const float* in, float* out, float* tmp, int n, int h
                            const float* noise_sigma, const unsigned* seeds, fsr_stream_t stream);
 int fsr_jpeg_roundtrip(const float* in, float* out, int n, int h, int w, const int* quality, int subsampling, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ strided element-wise losses (added within ABI 16: new entry points only)
+ * The pixel term of the training objective and the least-squares adversarial term.  a, b: float [n,c,h,w], each read through its OWN
+ * four strides (in elements; an NCHW view of an NHWC buffer, a planar batch, a slice) -- nothing is copied.  With d = a - b and
+ * count = n c h w:   loss[0] = sum psi(d) / count,   da = gscale[0] / count * psi'(d)   (gscale: device scalar, the upstream gradient;
+ * da is written through a's strides; b is the target and gets no gradient).
+ *   FSR_LOSS_L1           psi = |d|                   psi' = sign(d), 0 at d = 0
+ *   FSR_LOSS_SMOOTH_L1    fsr_smooth_l1_fwd / _bwd's expressions (beta 1)
+ *   FSR_LOSS_CHARBONNIER  psi = sqrt(d d + eps eps)   psi' = d / sqrt(d d + eps eps)        param = eps (positive, finite)
+ *   FSR_LOSS_MSE          psi = d d                   psi' = 2 d
+ * param is ignored by the other kinds.  The forward is one streaming launch (lanes = pixels, the channel loop inside the thread) plus
+ * the order-fixed second-level sum of at most 1024 workgroup partials in `scratch` (fsr_elem_loss_scratch() bytes): no float atomics.
+ * Refused with nothing launched: null pointers, non-positive extents, n c h w >= 2^31, an unknown kind, a Charbonnier eps that is not
+ * positive and finite, and -- over the axes longer than 1 -- negative, zero or overlapping strides of either operand. */
+enum { FSR_LOSS_L1 = 0, FSR_LOSS_SMOOTH_L1 = 1, FSR_LOSS_CHARBONNIER = 2, FSR_LOSS_MSE = 3 };
+size_t fsr_elem_loss_scratch(void);
+int fsr_elem_loss_fwd(int kind, float param, const float* a, long long sa_n, long long sa_c, long long sa_h, long long sa_w,
+                      const float* b, long long sb_n, long long sb_c, long long sb_h, long long sb_w, int n, int c, int h, int w,
+                      float* loss, void* scratch, fsr_stream_t stream);
+int fsr_elem_loss_bwd(int kind, float param, const float* a, long long sa_n, long long sa_c, long long sa_h, long long sa_w,
+                      const float* b, long long sb_n, long long sb_c, long long sb_h, long long sb_w, const float* gscale, float* da,
+                      int n, int c, int h, int w, fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ strided row-block copy (ABI 15; the banded tail)
  * A frame of H2 rows is covered by nwin = ceil(H2 / R) windows of Hw >= R + 4 rows: window k owns the core rows
  * [k R, min((k + 1) R, H2)) and starts at row s_k = clamp(k R - 2, 0, H2 - Hw).  The windows of all images are numbered
