@@ -588,25 +588,10 @@ __global__ __launch_bounds__(256) void tanh_bwd_image_kernel(const float* __rest
   }
 }
 
-template <typename T> T* P(void* p) { return (T*)p; }
-template <typename T> const T* P(const void* p) { return (const T*)p; }
-
-int check_c(const char* what, int dtype, int c) {
-  const int e = dtype == FSR_X3 ? 32 : (dtype != FSR_F32 ? 8 : 4);   // x3: whole hi / lo groups of 32 channels
-  if (dtype != FSR_F32 && dtype != FSR_BF16 && dtype != FSR_F16 && dtype != FSR_X3) return fsr_fail(-2, "%s: unknown dtype %d", what, dtype);
-  if (c <= 0 || c % e != 0) return fsr_fail(-2, "%s: channel count %d is not a multiple of %d", what, c, e);
-  return 0;
-}
-// x3 tensors: the split hi / lo addressing needs 128-byte aligned bases
-int check_x3(const char* what, int dtype, const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  if (dtype != FSR_X3) return 0;
-  if ((((size_t)a | (size_t)b | (size_t)c | (size_t)d) & 127) != 0) return fsr_fail(-2, "%s: x3 tensors must be 128-byte aligned", what);
-  return 0;
-}
 int check_reduce_c(const char* what, int dtype, int c) {
   int rc = check_c(what, dtype, c);
   if (rc) return rc;
-  const int cu = c / (dtype != FSR_F32 ? 8 : 4);
+  const int cu = c / fsr_unit_elems(dtype);
   if (cu > 256 || 256 % cu != 0) return fsr_fail(-2, "%s: %d channels do not tile a 256-thread workgroup", what, c);
   return 0;
 }
@@ -620,21 +605,6 @@ int slabs_for(int n, int hw) {
 
 }  // namespace
 
-#define FSR_DISPATCH_T(dtype, ...)                    \
-  if ((dtype) == FSR_BF16) {                          \
-    typedef bf16_t T;                                 \
-    __VA_ARGS__                                       \
-  } else if ((dtype) == FSR_F16) {                    \
-    typedef f16_t T;                                  \
-    __VA_ARGS__                                       \
-  } else if ((dtype) == FSR_X3) {                     \
-    typedef x3_t T;                                   \
-    __VA_ARGS__                                       \
-  } else {                                            \
-    typedef float T;                                  \
-    __VA_ARGS__                                       \
-  }
-
 extern "C" int fsr_instnorm_act_fwd(int dtype, const void* x, const float* stats, const void* res, int act, float slope,
                                     const float* prelu_weight, void* out, int n, int hw, int c, fsr_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -642,7 +612,7 @@ extern "C" int fsr_instnorm_act_fwd(int dtype, const void* x, const float* stats
   if (act == FSR_ACT_PRELU && !prelu_weight) return fsr_fail(-1, "fsr_instnorm_act_fwd: PReLU needs its weight");
   if (int rc = check_reduce_c("fsr_instnorm_act_fwd", dtype, c)) return rc;
   if (int rc = check_x3("fsr_instnorm_act_fwd", dtype, x, res, out)) return rc;
-  const long long units = (long long)hw * (c / (dtype != FSR_F32 ? 8 : 4));   // per image
+  const long long units = (long long)hw * (c / fsr_unit_elems(dtype));   // per image
   if (units >= (1LL << 31)) return fsr_fail(-2, "fsr_instnorm_act_fwd: image too large");
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(instnorm_act_fwd_kernel<T>, dim3(image_blocks(units, n), n), dim3(256), 0,
                                            stream, P<T>(x), stats, P<T>(res), act, slope, prelu_weight, P<T>(out), hw, c);)
@@ -682,7 +652,7 @@ extern "C" int fsr_instnorm_act_bwd_apply(int dtype, const void* g, const void* 
   if (act == FSR_ACT_PRELU && !prelu_weight) return fsr_fail(-1, "fsr_instnorm_act_bwd_apply: PReLU needs its weight");
   if (int rc = check_reduce_c("fsr_instnorm_act_bwd_apply", dtype, c)) return rc;
   if (int rc = check_x3("fsr_instnorm_act_bwd_apply", dtype, g, x, dx)) return rc;
-  const long long units = (long long)hw * (c / (dtype != FSR_F32 ? 8 : 4));
+  const long long units = (long long)hw * (c / fsr_unit_elems(dtype));
   if (units >= (1LL << 31)) return fsr_fail(-2, "fsr_instnorm_act_bwd_apply: image too large");
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(instnorm_act_bwd_apply_kernel<T>, dim3(image_blocks(units, n), n), dim3(256), 0,
                                            stream, P<T>(g), P<T>(x), stats, sums, act, slope, prelu_weight, P<T>(dx), hw, c);)
@@ -732,7 +702,7 @@ extern "C" int fsr_image_to_nhwc(int dtype, const float* img, long long sn, long
   if (!img || !out) return fsr_fail(-1, "fsr_image_to_nhwc: null argument");
   if (int rc = check_c("fsr_image_to_nhwc", dtype, cpad)) return rc;
   if (int rc = check_x3("fsr_image_to_nhwc", dtype, out)) return rc;
-  const int rowunits = w * (cpad / (dtype != FSR_F32 ? 8 : 4));
+  const int rowunits = w * (cpad / fsr_unit_elems(dtype));
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(image_to_nhwc_kernel<T>, dim3(n * h, row_blocks(rowunits)), dim3(256), 0, stream,
                                            img, sn, sc, sh, sw, h, w, scale0, scale1, scale2, shift0, shift1, shift2,
                                            P<T>(out), cpad);)
@@ -757,7 +727,7 @@ extern "C" int fsr_tanh_bwd_to_nhwc(int dtype, const float* g, long long sn, lon
   if (dbias && !scratch) return fsr_fail(-1, "fsr_tanh_bwd_to_nhwc: the bias gradient needs the scratch buffer");
   if (int rc = check_c("fsr_tanh_bwd_to_nhwc", dtype, cpad)) return rc;
   if (int rc = check_x3("fsr_tanh_bwd_to_nhwc", dtype, dz)) return rc;
-  const int rowunits = w * (cpad / (dtype != FSR_F32 ? 8 : 4));
+  const int rowunits = w * (cpad / fsr_unit_elems(dtype));
   const int gx = n * h < 512 ? n * h : 512, gy = row_blocks(rowunits);   // <= 512 x 64 workgroups
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(tanh_bwd_to_nhwc_kernel<T>, dim3(gx, gy), dim3(256), 0,
                                            stream, g, sn, sc, sh, sw, y_nhwc3, h, w, P<T>(dz), cpad, n * h,
@@ -784,11 +754,9 @@ extern "C" int fsr_tanh_bwd_image(const float* g, long long sn, long long sc, lo
 extern "C" int fsr_add(int dtype, const void* a, const void* b, void* out, long long count, fsr_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!a || !b || !out || count <= 0) return fsr_fail(-1, "fsr_add: bad argument");
-  if (dtype != FSR_F32 && dtype != FSR_BF16 && dtype != FSR_F16 && dtype != FSR_X3) return fsr_fail(-2, "fsr_add: unknown dtype %d", dtype);
-  const int e = dtype == FSR_X3 ? 32 : (dtype != FSR_F32 ? 8 : 4);
-  if (count % e) return fsr_fail(-2, "fsr_add: count %lld is not a multiple of %d", count, e);
+  if (int rc = check_count("fsr_add", dtype, count)) return rc;
   if (int rc = check_x3("fsr_add", dtype, a, b, out)) return rc;
-  const long long units = count / (dtype != FSR_F32 ? 8 : 4);
+  const long long units = count / fsr_unit_elems(dtype);
   long long blocks = (units + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(add_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, stream, P<T>(a), P<T>(b), P<T>(out), units);)
@@ -801,7 +769,7 @@ extern "C" int fsr_maxpool2_fwd(int dtype, const void* x, void* y, void* argmax,
   if (int rc = check_c("fsr_maxpool2_fwd", dtype, c)) return rc;
   if (int rc = check_x3("fsr_maxpool2_fwd", dtype, x, y)) return rc;
   if ((h | w) & 1) return fsr_fail(-2, "fsr_maxpool2_fwd: odd extent %dx%d", h, w);
-  const int rowunits = (w / 2) * (c / (dtype != FSR_F32 ? 8 : 4));
+  const int rowunits = (w / 2) * (c / fsr_unit_elems(dtype));
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_fwd_kernel<T>, dim3(n * (h / 2), row_blocks(rowunits)), dim3(256), 0,
                                            stream, P<T>(x), P<T>(y), (unsigned char*)argmax, h, w, c);)
   return fsr_check_launch("maxpool2_fwd_kernel");
@@ -814,7 +782,7 @@ extern "C" int fsr_maxpool2_bwd_argmax(int dtype, const void* g, const void* arg
   if (int rc = check_c("fsr_maxpool2_bwd_argmax", dtype, c)) return rc;
   if (int rc = check_x3("fsr_maxpool2_bwd_argmax", dtype, g, dx)) return rc;
   if ((h | w) & 1) return fsr_fail(-2, "fsr_maxpool2_bwd_argmax: odd extent %dx%d", h, w);
-  const int rowunits = (w / 2) * (c / (dtype != FSR_F32 ? 8 : 4));
+  const int rowunits = (w / 2) * (c / fsr_unit_elems(dtype));
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_idx_kernel<T>, dim3(n * (h / 2), row_blocks(rowunits)), dim3(256), 0,
                                            stream, P<T>(g), (const unsigned char*)argmax, P<T>(dx), h, w, c, relu_mask);)
   return fsr_check_launch("maxpool2_bwd_idx_kernel");
@@ -827,7 +795,7 @@ extern "C" int fsr_maxpool2_bwd(int dtype, const void* g, const void* x, const v
   if (int rc = check_c("fsr_maxpool2_bwd", dtype, c)) return rc;
   if (int rc = check_x3("fsr_maxpool2_bwd", dtype, g, x, y, dx)) return rc;
   if ((h | w) & 1) return fsr_fail(-2, "fsr_maxpool2_bwd: odd extent %dx%d", h, w);
-  const int rowunits = (w / 2) * (c / (dtype != FSR_F32 ? 8 : 4));
+  const int rowunits = (w / 2) * (c / fsr_unit_elems(dtype));
   FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool2_bwd_kernel<T>, dim3(n * (h / 2), row_blocks(rowunits)), dim3(256), 0,
                                            stream, P<T>(g), P<T>(x), P<T>(y), P<T>(dx), h, w, c, relu_mask);)
   return fsr_check_launch("maxpool2_bwd_kernel");

@@ -1,10 +1,10 @@
-// The AdamW element update shared by adamw_kernel / adamw_scaled_kernel (losses.hip) and adamw_ex_kernel (optim.hip).
+// The AdamW element update of adamw_kernel (optim.hip): its 128-bit loop, its scalar loop and all four instantiations.
 //
-// The three kernels are tested bit for bit against one another, and the library is built with -ffp-contract=fast, under which
-// a*b - c*d may become fma(a, b, -(c*d)) in one kernel and fma(-c, d, a*b) in another (the 128-bit form of optim.hip and the scalar
-// loops did differ that way).  So on the device every rounding is spelled out: the fused operations are explicit fmaf calls, and a
-// product that must be rounded on its own goes through FSR_ROUNDED, an empty asm statement the compiler cannot contract across.
-// The sequence is the one the two kernels of losses.hip have always compiled to:
+// Their results are pinned bit for bit (tests/golden/adamw_bits.npz, tests/test_optim_ex.py), and the library is built with
+// -ffp-contract=fast, under which a*b - c*d may become fma(a, b, -(c*d)) in one loop and fma(-c, d, a*b) in another (the 128-bit and
+// the scalar loop did differ that way).  So on the device every rounding is spelled out: the fused operations are explicit fmaf calls,
+// and a product that must be rounded on its own goes through FSR_ROUNDED, an empty asm statement the compiler cannot contract across.
+// The sequence is the one the first, scalar AdamW kernels compiled to, which the recorded bits come from:
 //   gi = g gs;  m' = fma(1 - b1, fma(gs, g, -m), m);  v' = rnd(v b2) + rnd(((1 - b2) gi) gi);
 //   denom = fma(sqrt(v'), rsqrt_bc2, eps);  p' = rnd(p fma(-lr, wd, 1)) - rnd((lr / bc1) (m' / denom)).
 // The host build of the emulator keeps the plain expressions (one rounding per operation).

@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "fsr_hip.h"
+
 struct ConvKArgs;
 
 // Records a message retrievable through fsr_last_error() and returns `code` (negative).
@@ -12,6 +14,46 @@ int fsr_fail(int code, const char* fmt, ...);
 int fsr_check_launch(const char* what);
 // Records the name of the kernel configuration a dispatch picked (fsr_last_kernel(): per-kernel attribution in bench.py).
 void fsr_note_kernel(const char* fmt, ...);
+
+// ---- dtype dispatch of the streaming kernels' host code (elementwise.hip, losses.hip): T is the element type inside the braces.
+// The last branch is float: the caller has refused unknown dtypes (fsr_known_dtype, check_c) BEFORE it dispatches.
+#define FSR_DISPATCH_T(dtype, ...)                    \
+  if ((dtype) == FSR_BF16) {                          \
+    typedef bf16_t T;                                 \
+    __VA_ARGS__                                       \
+  } else if ((dtype) == FSR_F16) {                    \
+    typedef f16_t T;                                  \
+    __VA_ARGS__                                       \
+  } else if ((dtype) == FSR_X3) {                     \
+    typedef x3_t T;                                   \
+    __VA_ARGS__                                       \
+  } else {                                            \
+    typedef float T;                                  \
+    __VA_ARGS__                                       \
+  }
+template <typename T> inline T* P(void* p) { return (T*)p; }
+template <typename T> inline const T* P(const void* p) { return (const T*)p; }
+
+inline bool fsr_known_dtype(int dtype) { return dtype == FSR_F32 || dtype == FSR_BF16 || dtype == FSR_F16 || dtype == FSR_X3; }
+inline int fsr_unit_elems(int dtype) { return dtype != FSR_F32 ? 8 : 4; }                     // elements per 16-byte unit
+inline int fsr_multiple(int dtype) { return dtype == FSR_X3 ? 32 : fsr_unit_elems(dtype); }   // x3: whole hi / lo groups of 32 channels
+inline int check_c(const char* what, int dtype, int c) {
+  if (!fsr_known_dtype(dtype)) return fsr_fail(-2, "%s: unknown dtype %d", what, dtype);
+  if (c <= 0 || c % fsr_multiple(dtype) != 0) return fsr_fail(-2, "%s: channel count %d is not a multiple of %d", what, c, fsr_multiple(dtype));
+  return 0;
+}
+// a flat tensor of `count` elements: whole units (x3: whole groups)
+inline int check_count(const char* what, int dtype, long long count) {
+  if (!fsr_known_dtype(dtype)) return fsr_fail(-2, "%s: unknown dtype %d", what, dtype);
+  if (count % fsr_multiple(dtype)) return fsr_fail(-2, "%s: count %lld is not a multiple of %d", what, count, fsr_multiple(dtype));
+  return 0;
+}
+// x3 tensors: the split hi / lo addressing needs 128-byte aligned bases
+inline int check_x3(const char* what, int dtype, const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  if (dtype != FSR_X3) return 0;
+  if ((((size_t)a | (size_t)b | (size_t)c | (size_t)d) & 127) != 0) return fsr_fail(-2, "%s: x3 tensors must be 128-byte aligned", what);
+  return 0;
+}
 
 // Planar-YUV output of h x w (yuv.hip; the encode entry points and the resampler): 4:2:0 needs even extents, 4:2:2 an even width, and
 // the matrix / range pair must be known.  0, or the refusal recorded in `who`'s name (`what`: a word put in front of the colour message).

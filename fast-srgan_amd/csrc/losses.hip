@@ -1,15 +1,13 @@
-// Loss reductions, the discriminator's 1x1 output convolution and the fused AdamW step.
+// Loss reductions and the discriminator's 1x1 output convolution.
 //
 //   BCEWithLogitsLoss (mean)        /root/reference/trainer.py:41,177,178,188
 //   SmoothL1Loss (beta 1, mean)     /root/reference/trainer.py:43,192 (VGG features), :109 (pixels)
 //   Conv2d(512 -> 1, k=1)           /root/reference/model.py:184-186
-//   AdamW(lr, fused=True)           /root/reference/trainer.py:33-38
 //
 // Reductions are wavefront-level: each lane accumulates a grid-stride partial, the 64 lanes are
 // summed with DPP/shuffle steps, the 4 waves of a workgroup meet in LDS and the workgroup's sum goes to
 // its slot of a scratch buffer; reduce.hip adds the slots in a fixed order (bit-reproducible losses and
 // gradients, no float atomics).
-#include "fsr_adamw.h"
 #include "fsr_common.h"
 #include "fsr_host.h"
 
@@ -156,103 +154,7 @@ __global__ __launch_bounds__(256) void conv1x1_c1_bwd_kernel(const float* __rest
   }
 }
 
-// The step count lives in device memory (a float) so that a captured hipGraph replays correctly: a tick kernel
-// increments it, the update kernel derives the bias corrections from it.
-__global__ void adamw_tick_kernel(float* __restrict__ step) {
-  if (threadIdx.x == 0) step[0] += 1.f;
-}
-
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long long count, float lr, float b1, float b2,
-                                                    float eps, float wd, const float* __restrict__ step, float gscale) {
-  const float t = step[0];
-  const float bc1 = 1.f - powf(b1, t);
-  const float rsqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, t));
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    fsr_adamw_update(pi, g[i], gscale, mi, vi, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-
-// ---- dynamic loss scaling (fp16 mode).  state: float[4] on the device = {scale, clean steps, non-finite flag, skipped steps}.
-// Everything is decided on the device, so a captured hipGraph keeps adapting while it replays.
-__global__ __launch_bounds__(256) void grad_nonfinite_kernel(const float* __restrict__ g, long long count, float* __restrict__ state) {
-  bool bad = false;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-    const float x = g[i];
-    bad |= !(fabsf(x) <= 3.0e38f);   // inf or NaN
-  }
-  if (bad) state[2] = 1.f;           // every writer stores the same value: no atomic needed
-}
-
-__global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, long long count, float lr, float b1, float b2,
-                                                           float eps, float wd, float* __restrict__ step, float gscale,
-                                                           const float* __restrict__ state) {
-  if (state[2] != 0.f) return;       // a gradient overflowed somewhere: no update at all, moments and step count untouched
-  const float t = step[0] + 1.f;     // (the step counter is advanced by adamw_tick_if_clean_kernel, enqueued behind this kernel)
-  const float gs = gscale / state[0];
-  const float bc1 = 1.f - powf(b1, t);
-  const float rsqrt_bc2 = 1.f / sqrtf(1.f - powf(b2, t));
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-    float pi = p[i], mi = m[i], vi = v[i];
-    fsr_adamw_update(pi, g[i], gs, mi, vi, lr, b1, b2, eps, wd, bc1, rsqrt_bc2);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = pi;
-  }
-}
-__global__ void adamw_tick_if_clean_kernel(float* __restrict__ step, const float* __restrict__ state) {
-  if (threadIdx.x == 0 && state[2] == 0.f) step[0] += 1.f;
-}
-__global__ void loss_scale_update_kernel(float* __restrict__ state, float growth_interval, float growth, float backoff) {
-  if (threadIdx.x != 0) return;
-  if (state[2] != 0.f) {             // overflow in this iteration: back off, start counting again
-    state[0] = fmaxf(state[0] * backoff, 1.f);
-    state[1] = 0.f;
-    state[3] += 1.f;
-    state[2] = 0.f;
-  } else {
-    state[1] += 1.f;
-    if (state[1] >= growth_interval) {
-      state[0] = fminf(state[0] * growth, 16777216.f);
-      state[1] = 0.f;
-    }
-  }
-}
-
 }  // namespace
-
-extern "C" int fsr_grad_nonfinite(const float* g, long long count, float* scale_state, fsr_stream_t stream_) {
-  if (!g || !scale_state || count <= 0) return fsr_fail(-1, "fsr_grad_nonfinite: bad argument");
-  long long blocks = (count + 256 * 8 - 1) / (256 * 8);
-  if (blocks > 1024) blocks = 1024;
-  hipLaunchKernelGGL(grad_nonfinite_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, g, count, scale_state);
-  return fsr_check_launch("grad_nonfinite_kernel");
-}
-
-extern "C" int fsr_adamw_step_scaled(float* p, const float* g, float* m, float* v, long long count, float lr, float beta1,
-                                     float beta2, float eps, float weight_decay, float* step_counter, float grad_scale,
-                                     const float* scale_state, fsr_stream_t stream_) {
-  if (!p || !g || !m || !v || !step_counter || !scale_state || count <= 0) return fsr_fail(-1, "fsr_adamw_step_scaled: bad argument");
-  long long blocks = (count + 256 * 4 - 1) / (256 * 4);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, g, m, v, count, lr, beta1,
-                     beta2, eps, weight_decay, step_counter, grad_scale, scale_state);
-  hipLaunchKernelGGL(adamw_tick_if_clean_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, step_counter, scale_state);
-  fsr_note_kernel("adamw_scaled_kernel");
-  return fsr_check_launch("adamw_scaled_kernel");
-}
-
-extern "C" int fsr_loss_scale_update(float* scale_state, float growth_interval, float growth, float backoff, fsr_stream_t stream_) {
-  if (!scale_state || !(growth_interval >= 1.f) || !(growth >= 1.f) || !(backoff > 0.f && backoff <= 1.f))
-    return fsr_fail(-1, "fsr_loss_scale_update: bad argument");
-  hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, scale_state, growth_interval, growth, backoff);
-  return fsr_check_launch("loss_scale_update_kernel");
-}
 
 extern "C" size_t fsr_loss_scratch(void) { return 1024 * sizeof(float); }   // red_blocks() caps the grid at 1024 workgroups
 
@@ -275,78 +177,35 @@ extern "C" int fsr_bce_logits_bwd(const float* x, const float* t, const float* g
 extern "C" int fsr_smooth_l1_fwd(int dtype, const void* a, const void* b, float* loss, void* scratch, long long count,
                                  fsr_stream_t stream_) {
   if (!a || !b || !loss || !scratch || count <= 0) return fsr_fail(-1, "fsr_smooth_l1_fwd: bad argument");
-  const int e = dtype != FSR_F32 ? 8 : 4;
-  if (count % (dtype == FSR_X3 ? 32 : e)) return fsr_fail(-2, "fsr_smooth_l1_fwd: count %lld is not a multiple of %d", count, dtype == FSR_X3 ? 32 : e);
-  if (dtype == FSR_X3 && ((((size_t)a | (size_t)b) & 127) != 0)) return fsr_fail(-2, "fsr_smooth_l1_fwd: x3 tensors must be 128-byte aligned");
-  const long long units = count / e;
+  if (int rc = check_count("fsr_smooth_l1_fwd", dtype, count)) return rc;
+  if (int rc = check_x3("fsr_smooth_l1_fwd", dtype, a, b)) return rc;
+  const long long units = count / fsr_unit_elems(dtype);
   const int blocks = red_blocks(units * 4);
-  if (dtype == FSR_F16)
-    hipLaunchKernelGGL(smooth_l1_fwd_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_,
-                       (const f16_t*)a, (const f16_t*)b, (float*)scratch, units);
-  else if (dtype == FSR_BF16)
-    hipLaunchKernelGGL(smooth_l1_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_,
-                       (const bf16_t*)a, (const bf16_t*)b, (float*)scratch, units);
-  else if (dtype == FSR_X3)
-    hipLaunchKernelGGL(smooth_l1_fwd_kernel<x3_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_,
-                       (const x3_t*)a, (const x3_t*)b, (float*)scratch, units);
-  else if (dtype == FSR_F32)
-    hipLaunchKernelGGL(smooth_l1_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_,
-                       (const float*)a, (const float*)b, (float*)scratch, units);
-  else
-    return fsr_fail(-2, "fsr_smooth_l1_fwd: unknown dtype %d", dtype);
+  FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(smooth_l1_fwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, P<T>(a), P<T>(b),
+                                           (float*)scratch, units);)
   if (int rc = fsr_check_launch("smooth_l1_fwd_kernel")) return rc;
   return fsr_launch_reduce_partials((const float*)scratch, loss, 1, blocks, 1, 1, 0, 0, 1.f / (float)count, 0, (hipStream_t)stream_);
 }
 extern "C" int fsr_smooth_l1_bwd(int dtype, const void* a, const void* b, const float* gscale, void* da, long long count,
                                  fsr_stream_t stream_) {
   if (!a || !b || !gscale || !da || count <= 0) return fsr_fail(-1, "fsr_smooth_l1_bwd: bad argument");
-  const int e = dtype != FSR_F32 ? 8 : 4;
-  if (count % (dtype == FSR_X3 ? 32 : e)) return fsr_fail(-2, "fsr_smooth_l1_bwd: count %lld is not a multiple of %d", count, dtype == FSR_X3 ? 32 : e);
-  if (dtype == FSR_X3 && ((((size_t)a | (size_t)b | (size_t)da) & 127) != 0)) return fsr_fail(-2, "fsr_smooth_l1_bwd: x3 tensors must be 128-byte aligned");
-  const long long units = count / e;
-  if (dtype == FSR_F16)
-    hipLaunchKernelGGL(smooth_l1_bwd_kernel<f16_t>, dim3(red_blocks(units * 4)), dim3(256), 0, (hipStream_t)stream_,
-                       (const f16_t*)a, (const f16_t*)b, gscale, (f16_t*)da, units, 1.f / (float)count);
-  else if (dtype == FSR_BF16)
-    hipLaunchKernelGGL(smooth_l1_bwd_kernel<bf16_t>, dim3(red_blocks(units * 4)), dim3(256), 0, (hipStream_t)stream_,
-                       (const bf16_t*)a, (const bf16_t*)b, gscale, (bf16_t*)da, units, 1.f / (float)count);
-  else if (dtype == FSR_X3)
-    hipLaunchKernelGGL(smooth_l1_bwd_kernel<x3_t>, dim3(red_blocks(units * 4)), dim3(256), 0, (hipStream_t)stream_,
-                       (const x3_t*)a, (const x3_t*)b, gscale, (x3_t*)da, units, 1.f / (float)count);
-  else if (dtype == FSR_F32)
-    hipLaunchKernelGGL(smooth_l1_bwd_kernel<float>, dim3(red_blocks(units * 4)), dim3(256), 0, (hipStream_t)stream_,
-                       (const float*)a, (const float*)b, gscale, (float*)da, units, 1.f / (float)count);
-  else
-    return fsr_fail(-2, "fsr_smooth_l1_bwd: unknown dtype %d", dtype);
+  if (int rc = check_count("fsr_smooth_l1_bwd", dtype, count)) return rc;
+  if (int rc = check_x3("fsr_smooth_l1_bwd", dtype, a, b, da)) return rc;
+  const long long units = count / fsr_unit_elems(dtype);
+  FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(smooth_l1_bwd_kernel<T>, dim3(red_blocks(units * 4)), dim3(256), 0, (hipStream_t)stream_,
+                                           P<T>(a), P<T>(b), gscale, P<T>(da), units, 1.f / (float)count);)
   return fsr_check_launch("smooth_l1_bwd_kernel");
-}
-
-static int c1_check(const char* what, int dtype, int c, const void* x, const void* dx = nullptr) {
-  if (dtype != FSR_F32 && dtype != FSR_BF16 && dtype != FSR_F16 && dtype != FSR_X3) return fsr_fail(-2, "%s: unknown dtype %d", what, dtype);
-  if (dtype == FSR_X3 && ((((size_t)x | (size_t)dx) & 127) != 0)) return fsr_fail(-2, "%s: x3 tensors must be 128-byte aligned", what);
-  const int e = dtype == FSR_X3 ? 32 : (dtype != FSR_F32 ? 8 : 4);
-  if (c <= 0 || c % e) return fsr_fail(-2, "%s: %d channels is not a multiple of %d", what, c, e);
-  return 0;
 }
 
 extern "C" int fsr_conv1x1_c1_fwd(int dtype, const void* x, const float* w, const float* b, float* logits, int npix, int c,
                                   fsr_stream_t stream_) {
   if (!x || !w || !b || !logits || npix <= 0) return fsr_fail(-1, "fsr_conv1x1_c1_fwd: bad argument");
-  if (int rc = c1_check("fsr_conv1x1_c1_fwd", dtype, c, x)) return rc;
+  if (int rc = check_c("fsr_conv1x1_c1_fwd", dtype, c)) return rc;
+  if (int rc = check_x3("fsr_conv1x1_c1_fwd", dtype, x)) return rc;
   int blocks = (npix + 3) / 4;
   if (blocks > 2048) blocks = 2048;
-  if (dtype == FSR_F16)
-    hipLaunchKernelGGL(conv1x1_c1_fwd_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const f16_t*)x, w,
-                       b, logits, npix, c);
-  else if (dtype == FSR_BF16)
-    hipLaunchKernelGGL(conv1x1_c1_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const bf16_t*)x, w,
-                       b, logits, npix, c);
-  else if (dtype == FSR_X3)
-    hipLaunchKernelGGL(conv1x1_c1_fwd_kernel<x3_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const x3_t*)x, w,
-                       b, logits, npix, c);
-  else
-    hipLaunchKernelGGL(conv1x1_c1_fwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, (const float*)x, w, b,
-                       logits, npix, c);
+  FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(conv1x1_c1_fwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, P<T>(x), w, b,
+                                           logits, npix, c);)
   return fsr_check_launch("conv1x1_c1_fwd_kernel");
 }
 
@@ -355,41 +214,19 @@ extern "C" size_t fsr_conv1x1_c1_bwd_scratch(int c) { return c > 0 ? (size_t)512
 extern "C" int fsr_conv1x1_c1_bwd(int dtype, const float* g, const void* x, const float* w, void* dx, float* dw, float* db,
                                   void* scratch, int npix, int c, fsr_stream_t stream_) {
   if (!g || !x || !w || !dw || !db || !scratch || npix <= 0) return fsr_fail(-1, "fsr_conv1x1_c1_bwd: bad argument");
-  if (int rc = c1_check("fsr_conv1x1_c1_bwd", dtype, c, x, dx)) return rc;
-  const int cu = c / (dtype != FSR_F32 ? 8 : 4);
+  if (int rc = check_c("fsr_conv1x1_c1_bwd", dtype, c)) return rc;
+  if (int rc = check_x3("fsr_conv1x1_c1_bwd", dtype, x, dx)) return rc;
+  const int cu = c / fsr_unit_elems(dtype);
   if (cu > 256 || 256 % cu) return fsr_fail(-2, "fsr_conv1x1_c1_bwd: %d channels do not tile a 256-thread workgroup", c);
   const int rows = 256 / cu;
   int blocks = (npix + rows * 8 - 1) / (rows * 8);
   if (blocks > 512) blocks = 512;
   if (blocks < 1) blocks = 1;
   float* part = (float*)scratch;   // [blocks][c + 1]: weight-gradient partials, then the bias-gradient partial
-  if (dtype == FSR_F16)
-    hipLaunchKernelGGL(conv1x1_c1_bwd_kernel<f16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, g, (const f16_t*)x,
-                       w, (f16_t*)dx, part, npix, c);
-  else if (dtype == FSR_BF16)
-    hipLaunchKernelGGL(conv1x1_c1_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, g, (const bf16_t*)x,
-                       w, (bf16_t*)dx, part, npix, c);
-  else if (dtype == FSR_X3)
-    hipLaunchKernelGGL(conv1x1_c1_bwd_kernel<x3_t>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, g, (const x3_t*)x,
-                       w, (x3_t*)dx, part, npix, c);
-  else
-    hipLaunchKernelGGL(conv1x1_c1_bwd_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, g, (const float*)x, w,
-                       (float*)dx, part, npix, c);
+  FSR_DISPATCH_T(dtype, hipLaunchKernelGGL(conv1x1_c1_bwd_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, g, P<T>(x), w,
+                                           P<T>(dx), part, npix, c);)
   if (int rc = fsr_check_launch("conv1x1_c1_bwd_kernel")) return rc;
   // dw[c] and db[0] from the same partial rows (row stride c + 1)
   if (int rc = fsr_launch_reduce_partials(part, dw, 1, blocks, c, c + 1, 0, 0, 1.f, 0, (hipStream_t)stream_)) return rc;
   return fsr_launch_reduce_partials(part + c, db, 1, blocks, 1, c + 1, 0, 0, 1.f, 0, (hipStream_t)stream_);
-}
-
-extern "C" int fsr_adamw_step(float* p, const float* g, float* m, float* v, long long count, float lr, float beta1,
-                              float beta2, float eps, float weight_decay, float* step_counter, float grad_scale,
-                              fsr_stream_t stream_) {
-  if (!p || !g || !m || !v || !step_counter || count <= 0) return fsr_fail(-1, "fsr_adamw_step: bad argument");
-  hipLaunchKernelGGL(adamw_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream_, step_counter);
-  long long blocks = (count + 256 * 4 - 1) / (256 * 4);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream_, p, g, m, v, count, lr, beta1,
-                     beta2, eps, weight_decay, step_counter, grad_scale);
-  fsr_note_kernel("adamw_kernel");
-  return fsr_check_launch("adamw_kernel");
 }

@@ -202,23 +202,18 @@ class ArenaAdamW(torch.optim.Optimizer):
         if self.scale_state is not None:
             L.check(L.lib().fsr_grad_nonfinite(_p(self.flat_grad), self.flat_grad.numel(), _p(self.scale_state), _stream()),
                     "fsr_grad_nonfinite")
+        arena = (_p(self.flat_param), _p(self.flat_grad), _p(self.exp_avg), _p(self.exp_avg_sq))
+        n = self.flat_param.numel()
+        hyper = (float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), _p(self.step_dev),
+                 float(self.grad_scale))
+        state = None if self.scale_state is None else _p(self.scale_state)
         if self._sched is not None:
-            L.check(L.lib().fsr_adamw_step_ex(_p(self.flat_param), _p(self.flat_grad), _p(self.exp_avg), _p(self.exp_avg_sq),
-                                              None if self.ema is None else _p(self.ema), self.flat_param.numel(), _p(self._sched),
-                                              float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                                              _p(self.step_dev), float(self.grad_scale),
-                                              None if self.scale_state is None else _p(self.scale_state), float(self.ema_decay),
-                                              _stream()), "fsr_adamw_step_ex")
-        elif self.scale_state is not None:
-            L.check(L.lib().fsr_adamw_step_scaled(_p(self.flat_param), _p(self.flat_grad), _p(self.exp_avg), _p(self.exp_avg_sq),
-                                                  self.flat_param.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                                  float(g["eps"]), float(g["weight_decay"]), _p(self.step_dev),
-                                                  float(self.grad_scale), _p(self.scale_state), _stream()), "fsr_adamw_step_scaled")
+            L.check(L.lib().fsr_adamw_step_ex(*arena, None if self.ema is None else _p(self.ema), n, _p(self._sched), *hyper, state,
+                                              float(self.ema_decay), _stream()), "fsr_adamw_step_ex")
+        elif state is not None:
+            L.check(L.lib().fsr_adamw_step_scaled(*arena, n, float(g["lr"]), *hyper, state, _stream()), "fsr_adamw_step_scaled")
         else:
-            L.check(L.lib().fsr_adamw_step(_p(self.flat_param), _p(self.flat_grad), _p(self.exp_avg), _p(self.exp_avg_sq),
-                                           self.flat_param.numel(), float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                           float(g["eps"]), float(g["weight_decay"]), _p(self.step_dev), float(self.grad_scale),
-                                           _stream()), "fsr_adamw_step")
+            L.check(L.lib().fsr_adamw_step(*arena, n, float(g["lr"]), *hyper, _stream()), "fsr_adamw_step")
         # the kernel writes through raw pointers, so torch's version counters do not move: publish an
         # epoch the packed-filter cache (ops.packed_filter) keys on instead
         for p in self._params + self._ema_params:

@@ -425,8 +425,9 @@ int fsr_quality_u8(const unsigned char* a, long long a_image_bytes, long long a_
 /* ------------------------------------------------------------------ AdamW (trainer.py:33-38, torch defaults)
  * One fused step over a flat float parameter arena: g' = g*grad_scale (1/world_size after a SUM all-reduce);
  * p *= 1 - lr*wd; m, v updated; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  `step_counter` is a DEVICE float
- * holding the number of steps taken so far: the call first increments it on the device, then derives the
- * bias corrections bc1 = 1 - beta1^t, bc2 = 1 - beta2^t from it (host-free, so a captured hipGraph replays). */
+ * holding the number of steps taken so far: the update derives the bias corrections bc1 = 1 - beta1^t, bc2 = 1 - beta2^t
+ * from t = step_counter + 1 and a one-thread launch behind it increments the counter (host-free, so a captured hipGraph replays).
+ * Any float pointers are accepted; 16-byte aligned ones take 128-bit loads and stores. */
 int fsr_adamw_step(float* p, const float* g, float* m, float* v, long long count, float lr, float beta1, float beta2,
                    float eps, float weight_decay, float* step_counter, float grad_scale, fsr_stream_t stream);
 
@@ -461,11 +462,11 @@ int fsr_loss_scale_update(float* scale_state, float growth_interval, float growt
  *   constant / multistep:  val = values[#{boundaries <= e}]
  *   cosine:                val = min + 0.5 (base - min) (1 + cosf(pi fminf(e, T) / T))
  *   lr = e < W ? val ((e + 1) / W) : val
- * and is, with that lr, exactly fsr_adamw_step's arithmetic (scale_state NULL: step counter and clock both advance by one) or
- * fsr_adamw_step_scaled's (scale_state given: g' = g*grad_scale/S; while the non-finite flag is up NOTHING changes -- p, m, v, ema,
- * step counter, clock and lr_used stay bit-identical -- else step counter and clock advance by one).
- * ema (nullable, `count` floats): after p' is computed, ema += (p' - ema) (1 - ema_decay), ema_decay in [0, 1).
- * Any float pointers are accepted; 16-byte aligned ones take 128-bit loads and stores. */
+ * and is, with that lr, the same kernel as fsr_adamw_step (scale_state NULL: step counter and clock both advance by one) or
+ * fsr_adamw_step_scaled (scale_state given: g' = g*grad_scale/S; while the non-finite flag is up NOTHING changes -- p, m, v, ema,
+ * step counter, clock and lr_used stay bit-identical -- else step counter and clock advance by one): all three entry points launch
+ * one kernel template, which differs only in where the rate comes from, so their results are equal bit for bit.
+ * ema (nullable, `count` floats): after p' is computed, ema += (p' - ema) (1 - ema_decay), ema_decay in [0, 1). */
 #define FSR_SCHED_WORDS 32
 #define FSR_SCHED_KIND 0
 #define FSR_SCHED_BASE 1

@@ -1,4 +1,5 @@
-// Stand-alone host program for sanitizer runs of fsr_adamw_step_ex: csrc/optim.hip compiled through the emulator's headers, no Python.
+// Stand-alone host program for sanitizer runs of every entry point of csrc/optim.hip (fsr_adamw_step, fsr_adamw_step_scaled,
+// fsr_adamw_step_ex, fsr_grad_nonfinite, fsr_loss_scale_update), compiled through the emulator's headers, no Python.
 //
 //   E=tests/emu; C=fast-srgan_amd/csrc
 //   clang++ -x c++ -std=c++17 -O1 -g -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined \
@@ -7,7 +8,8 @@
 // (detect_leaks=0: the emulator keeps its fiber stacks for the next launch and never frees the last set, emu_runtime.cpp run_workgroups.)
 //
 // Every buffer is a heap allocation of EXACTLY the bytes the call may touch (a read or write one element past the end is
-// reported), at counts 1, 5 and 1025, 16-byte aligned and offset by one float, with and without the EMA and the loss-scale state.
+// reported), at counts 1, 5 and 1025, 16-byte aligned and offset by one float, with and without the EMA and the loss-scale state;
+// the by-value entry points and the loss-scale pair run on the same buffers behind the ten block-rate steps.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -77,6 +79,24 @@ int main() {
           if (step[0] != 10.f || sched[FSR_SCHED_CLOCK] != 10.f || sched[FSR_SCHED_LR_USED] != sched[FSR_SCHED_VALUES + 8] || !(p[offset] == p[offset])) {
             fprintf(stderr, "count %lld offset %d: step %g clock %g lr_used %g\n", n, offset, step[0], sched[FSR_SCHED_CLOCK], sched[FSR_SCHED_LR_USED]);
             return 1;
+          }
+          // the by-value entry points on the same buffers (once per EMA setting is enough: they take none), then the loss-scale pair
+          if (!with_ema) {
+            const int rc = scaled ? (fsr_grad_nonfinite(g + offset, n, state, nullptr) ||
+                                     fsr_adamw_step_scaled(p + offset, g + offset, m + offset, v + offset, n, 1e-4f, 0.9f, 0.999f, 1e-8f, 0.01f,
+                                                           step, 1.f, state, nullptr) ||
+                                     fsr_loss_scale_update(state, 2.f, 2.f, 0.5f, nullptr))
+                                  : fsr_adamw_step(p + offset, g + offset, m + offset, v + offset, n, 1e-4f, 0.9f, 0.999f, 1e-8f, 0.01f, step, 1.f,
+                                                   nullptr);
+            if (rc != 0) {
+              fprintf(stderr, "by-value entry point failed: %s\n", g_err);
+              return 1;
+            }
+            calls += scaled ? 3 : 1;
+            if (step[0] != 11.f || sched[FSR_SCHED_CLOCK] != 10.f || (scaled && (state[1] != 1.f || state[2] != 0.f)) || !(p[offset] == p[offset])) {
+              fprintf(stderr, "count %lld offset %d by value: step %g clock %g\n", n, offset, step[0], sched[FSR_SCHED_CLOCK]);
+              return 1;
+            }
           }
           free(p), free(g), free(m), free(v), free(e), free(sched), free(step), free(state);
         }

@@ -1,7 +1,8 @@
 """fsr_adamw_step_ex through the C ABI: the AdamW step with a device-side learning-rate schedule and a fused EMA.
 
 The update itself carries NO tolerance anywhere in this file: with the learning rate the kernel reports in lr_used, p, m, v and the step
-counter are compared bit for bit with fsr_adamw_step / fsr_adamw_step_scaled (the kernels tests/test_stream_exact.py holds to float64)
+counter are compared bit for bit with fsr_adamw_step / fsr_adamw_step_scaled (the by-value entry points, which
+tests/test_stream_exact.py holds to float64 and tests/test_adamw_bits.py to recorded bits: another instantiation of the same template)
 on copies of the same inputs -- at every vector tail length, one workgroup + 1, past the grid cap and through pointers that are not
 16-byte aligned.  What is left is the rate and the average:
 
@@ -87,7 +88,7 @@ def _block(dev, *a, **k):
 
 
 class _Twin:
-    """Two copies of one problem: `a` stepped by fsr_adamw_step_ex, `b` by the old entry point at the rate `a` reports."""
+    """Two copies of one problem: `a` stepped by fsr_adamw_step_ex, `b` by the by-value entry point at the rate `a` reports."""
 
     def __init__(self, dev, step0, count, scaled=False, offset=0, ema=None):
         p, g, m, v = _inputs(step0, count)
@@ -112,7 +113,7 @@ class _Twin:
         return w[C.LR_USED], w[C.CLOCK]
 
 
-# ------------------------------------------------------------------------------------------------- bit identity with the existing kernels
+# ------------------------------------------------------------------------------------------------- bit identity with the by-value entry points
 @pytest.mark.parametrize("scaled", (False, True))
 @pytest.mark.parametrize("count", COUNTS)
 @pytest.mark.parametrize("wd", (0.0, 0.01))
@@ -180,7 +181,7 @@ def _lr_rows():
 
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_warmup_on_multistep(backend):
-    """W = 4 over milestones (2, 3, 7): lr = val (e + 1) / 4 for the first four updates; the update again bit-equal to the old kernel's."""
+    """W = 4 over milestones (2, 3, 7): lr = val (e + 1) / 4 for the first four updates; the update again bit-equal to the by-value entry point's."""
     dev = select(backend)
     T = _Twin(dev, 0, 1029)
     sched = _block(dev, **WARMUP_MULTISTEP)
@@ -259,7 +260,7 @@ def _ema_units(got, ema_before, p_new):
 @pytest.mark.parametrize("backend", BACKENDS)
 def test_ema_general_over_three_steps(backend, scaled):
     """decay 0.999 over 3 consecutive steps of the AdamW case: ema' within K_EMA units of the float64 contract evaluated from the ema
-    before the step and the kernel's OWN float32 p'; p, m, v bit-equal to the old kernel's all along."""
+    before the step and the kernel's OWN float32 p'; p, m, v bit-equal to the by-value entry point's all along."""
     dev = select(backend)
     T = _Twin(dev, 9, EMA_COUNT, scaled, ema=_ema_start(EMA_COUNT))
     sched = _block(dev, "constant", 1e-4)

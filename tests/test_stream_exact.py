@@ -1,4 +1,4 @@
-"""Float64-referenced parity of the HBM-bound kernels (elementwise.hip), the losses / 1x1 convolution / AdamW (losses.hip) and the
+"""Float64-referenced parity of the HBM-bound kernels (elementwise.hip), the losses / 1x1 convolution (losses.hip), AdamW (optim.hip) and the
 second-level reduce (reduce.hip), called through the C ABI at the shapes where each kernel takes another path.
 
 test_exact.py covers the convolution families with integer inputs and no tolerance.  The kernels here divide, take square roots

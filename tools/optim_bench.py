@@ -1,12 +1,14 @@
 """Device time of the AdamW step with and without the device-side schedule and the fused EMA.
 
-    python tools/optim_bench.py [--rounds 30] [--inner 10] [--out profiles/optim_bench.txt]
+    python tools/optim_bench.py [--rounds 30] [--inner 10] [--against OTHER/libfsr_hip.so] [--out profiles/optim_bench.txt]
 
-At the generator's and the discriminator's real arena sizes (read from freshly built default networks): fsr_adamw_step (the kernel every
-default run uses: the yardstick), fsr_adamw_step_ex with a constant schedule (128-bit accesses), the same through pointers one float off
-their allocations (its scalar path), and the same with the EMA.  Each from its own device events around --inner calls.  The candidates
+At the generator's and the discriminator's real arena sizes (read from freshly built default networks): fsr_adamw_step (the rate by
+value, what every default run calls: the yardstick), fsr_adamw_step_scaled (the same under the fp16 loss scale), fsr_adamw_step_ex with
+a constant schedule (the same kernel with the rate read from the block), that through pointers one float off their allocations (the
+scalar path), and with the EMA.  Each from its own device events around --inner calls.  The candidates
 are INTERLEAVED: every round times each of them once, in turn, so clock and thermal drift fall on all of them alike; the figure is the
-median over the rounds, the spread the 10th to 90th percentile.  Nothing is gated on it."""
+median over the rounds, the spread the 10th to 90th percentile.  --against: the two by-value legs of another build of the library
+(an A/B of the default path's launches) join the same rounds.  Nothing is gated on it."""
 import argparse
 import importlib
 import os
@@ -38,9 +40,11 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--inner", type=int, default=10, help="calls per timed interval")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "optim_bench.txt"))
+    ap.add_argument("--against", default=None, help="another build of libfsr_hip.so: its by-value legs are interleaved with this build's")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     lib = L.lib()
+    other = L._bind(a.against) if a.against else None
     lines = ["# tools/optim_bench.py --rounds %d --inner %d on %s" % (a.rounds, a.inner, torch.cuda.get_device_name(0)),
              "# us per call: median over the rounds [p10 .. p90]; candidates interleaved round by round; MB = bytes read + written; each call",
              "# includes its one-thread tick launch",
@@ -54,17 +58,27 @@ def main(argv=None):
         step = torch.zeros(1, device=dev)
         sched = optim.LRSchedule("constant", base_lr=1e-4).words().to(dev)
 
-        def old(off=0):
-            p, g, m, v = (buf[k][off:off + n].data_ptr() for k in "pgmv")
-            L.check(lib.fsr_adamw_step(p, g, m, v, n, 1e-4, *HP, step.data_ptr(), 1.0, ops._stream()), "fsr_adamw_step")
+        state = torch.tensor([1024.0, 0.0, 0.0, 0.0], device=dev)
+
+        def by_value(scaled=False, lib=lib):
+            p, g, m, v = (buf[k][:n].data_ptr() for k in "pgmv")
+            if scaled:
+                L.check(lib.fsr_adamw_step_scaled(p, g, m, v, n, 1e-4, *HP, step.data_ptr(), 1.0, state.data_ptr(), ops._stream()),
+                        "fsr_adamw_step_scaled")
+            else:
+                L.check(lib.fsr_adamw_step(p, g, m, v, n, 1e-4, *HP, step.data_ptr(), 1.0, ops._stream()), "fsr_adamw_step")
 
         def ex(off=0, ema=False):
             p, g, m, v, e = (buf[k][off:off + n].data_ptr() for k in "pgmve")
             L.check(lib.fsr_adamw_step_ex(p, g, m, v, e if ema else None, n, sched.data_ptr(), *HP, step.data_ptr(), 1.0, None, 0.999,
                                           ops._stream()), "fsr_adamw_step_ex")
 
-        cands = [("fsr_adamw_step", old, 28), ("fsr_adamw_step_ex constant, x4", ex, 28), ("fsr_adamw_step_ex constant, x1", lambda: ex(1), 28),
+        cands = [("fsr_adamw_step", by_value, 28), ("fsr_adamw_step_scaled", lambda: by_value(True), 28),
+                 ("fsr_adamw_step_ex constant, x4", ex, 28), ("fsr_adamw_step_ex constant, x1", lambda: ex(1), 28),
                  ("fsr_adamw_step_ex constant + EMA, x4", lambda: ex(0, True), 36)]
+        if other is not None:
+            cands += [("--against: fsr_adamw_step", lambda: by_value(False, other), 28),
+                      ("--against: fsr_adamw_step_scaled", lambda: by_value(True, other), 28)]
         for _, fn, _ in cands:                          # warm-up: code objects
             for _ in range(3):
                 fn()
