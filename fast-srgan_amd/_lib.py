@@ -22,6 +22,9 @@ SITING_JPEG, SITING_MPEG2 = 0, 1             # chroma siting of fsr_i420_to_imag
 CHROMA_420, CHROMA_422, CHROMA_444 = 0, 1, 2     # chroma subsampling of the fsr_*_yuv entry points
 LAYOUT_PLANAR, LAYOUT_NV12 = 0, 1                # payload layout of the fsr_*_yuv_ex entry points
 BLUR_MAX_RADIUS, BLUR_TAPS = 9, 19               # fsr_degrade_blur_noise
+FILTER2D_MAX_RADIUS, FILTER2D_TAPS = 10, 441     # fsr_filter2d: the largest radius, and the per-sample pitch of its tap tables
+FILTER2D_TILE_H, FILTER2D_TILE_W = 32, 64        # fsr_filter2d: the outputs one workgroup owns
+NOISE_SHOT, NOISE_GREY = 1, 2                    # fsr_degrade_noise_kinds: flag bits of a sample
 QUALITY_Y, QUALITY_RGB = 0, 1                    # fsr_quality_u8
 LOSS_L1, LOSS_SMOOTH_L1, LOSS_CHARBONNIER, LOSS_MSE = 0, 1, 2, 3    # fsr_elem_loss_fwd / _bwd
 OPT_BIAS, OPT_PRELU, OPT_OSCALE, OPT_MASK, OPT_PREACT, OPT_STATS = 1, 2, 4, 8, 16, 32   # fsr_conv3x3_pack_block
@@ -131,6 +134,9 @@ SIGNATURES = {
     "fsr_copy_rows": (c_int, [P, c_ll, P, c_ll, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "fsr_degrade_blur_noise": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "fsr_jpeg_roundtrip": (c_int, [P, P, c_int, c_int, c_int, P, c_int, P]),
+    "fsr_filter2d": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),
+    "fsr_resize_select": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int, c_int, P, P]),
+    "fsr_degrade_noise_kinds": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P]),
 }
 
 _lib = None

@@ -15,6 +15,13 @@ and the fp16 loss scaler:
 degradation of the LR batches on the device.  The keys are NOT in configs/config.yaml (it keeps the reference's keys and values) and
 have no entry in DEFAULTS: train.make_degradation reads them with defaults of "off", and an override of a key the file lacks
 (`data.degradation.jpeg_prob=0.7`, `data.degradation.jpeg_quality=[30,95]`) creates the groups on its way.
+The high-order model, off by default like the rest: `data.degradation.{kernel_prob, kernel_size, kernel_kinds, kernel_sigma,
+kernel_beta_generalized, kernel_beta_plateau, sinc_prob}` (a blur kernel drawn per sample from a bank -- iso / aniso Gaussian, generalised
+and plateau shapes, sinc -- applied to the HR crop in front of the down-scale; kernel_kinds: six weights in that order),
+`resize_filters=[bicubic, bilinear, area]` (draw weights of the down-scale filter), `noise_shot_prob`, `noise_shot_gain`, `noise_grey_prob`
+(how often a sample's noise is shot noise of that gain, and grey), the group `data.degradation.second.{kernel_*, sinc_prob, noise_*, jpeg_prob,
+jpeg_quality}` (a second blur -> noise -> JPEG round at LR resolution) and `final_sinc_prob`, `final_sinc_size=[7,21]` (a sinc filter of an
+odd size from that range, in LR pixels, before or behind the last JPEG).
 
 `data.augment.dihedral` (default false): random flips and 90-degree rotations of the training crops on the device, one of
 the 8 transform codes per sample.  An extension key of the same kind: not in configs/config.yaml or DEFAULTS, read by

@@ -3,6 +3,8 @@
 // second; a template form of it is the noise-only launch), and a JPEG round trip without the entropy coder in which a workgroup owns
 // 16x16 pixels -- one 4:2:0 MCU, or four 4:4:4 MCUs -- and runs colour transform, DCT, quantisation and the inverse out of LDS.
 // The launch sequence never depends on the parameters drawn: a sample whose stage is off passes through the same launches as a copy.
+// The high-order model adds a per-sample K x K filter out of LDS (filter2d_kernel), a separable resize with a tap table
+// chosen per sample, and the noise-only launch with a kind (shot, grey) per sample.
 #include "fsr_common.h"
 #include "fsr_host.h"
 
@@ -56,12 +58,14 @@ __global__ __launch_bounds__(256) void blur_hpass_kernel(const float* __restrict
 }
 
 // pass 2 (BLUR): out = sum_j taps[n][j + r] * tmp[clamp(y + j)][x]; then (NOISE) out += z * sigma_n * (2 / 255).  BLUR = false is the
-// noise-only launch: `src` is the input itself.
-template <bool BLUR, bool NOISE>
+// noise-only launch: `src` is the input itself.  KINDS reads a flag word per sample beside its strength: FSR_NOISE_SHOT
+// scales z by sqrt(g v) of the element's own code v (the normal approximation of shot noise), FSR_NOISE_GREY hashes y w + x so that the
+// channels of a pixel share z; without a flag the arithmetic is that of KINDS = false.
+template <bool BLUR, bool NOISE, bool KINDS = false>
 __global__ __launch_bounds__(256) void blur_vpass_noise_kernel(const float* __restrict__ src, float* __restrict__ out, int h, int w,
                                                                const float* __restrict__ taps, const int* __restrict__ radii,
                                                                const float* __restrict__ noise_sigma, const unsigned* __restrict__ seeds,
-                                                               long long total) {
+                                                               const int* __restrict__ flags, long long total) {
   const long long plane3 = 3LL * h * w;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int n = (int)(i / plane3);
@@ -83,7 +87,16 @@ __global__ __launch_bounds__(256) void blur_vpass_noise_kernel(const float* __re
     }
     if constexpr (NOISE) {
       const float sg = noise_sigma[n];
-      if (sg > 0.f) s = fmaf(hash_normal(seeds[2 * n], seeds[2 * n + 1], e), sg * (2.0f / 255.0f), s);
+      if (sg > 0.f) {
+        float amp = sg;
+        unsigned ei = e;
+        if constexpr (KINDS) {
+          const int f = flags[n];
+          if (f & FSR_NOISE_GREY) ei = e % ((unsigned)h * (unsigned)w);
+          if (f & FSR_NOISE_SHOT) amp = sqrtf(sg * fminf(fmaxf((s + 1.0f) * 127.5f, 0.f), 255.f));
+        }
+        s = fmaf(hash_normal(seeds[2 * n], seeds[2 * n + 1], ei), amp * (2.0f / 255.0f), s);
+      }
     }
     out[i] = s;
   }
@@ -233,6 +246,152 @@ __global__ __launch_bounds__(256) void jpeg_roundtrip_kernel(const float* __rest
   out[dst + 2 * plane] = fminf(fmaxf(rintf(bo), 0.f), 255.f) / 127.5f - 1.0f;
 }
 
+// ---------------------------------------------------------------------------------------------- per-sample K x K filter
+// out[n][c][y][x] = sum_dy sum_dx k_n[dy + r][dx + r] in[n][c][clamp(y + dy)][clamp(x + dx)], K = 2 r + 1 <= 21.  One workgroup owns
+// FSR_FILTER2D_TILE_H x FSR_FILTER2D_TILE_W outputs of one (sample, channel): it stages the tile and its r-pixel halo in LDS once, the
+// borders already clamped, then thread (t / 8, t % 8) produces the 8 adjacent outputs of row t / 8 that start at column 8 (t % 8).  Per
+// kernel row it reads its 8 + 2 r source values from LDS into registers once (16-byte reads: the pitch and the run start are multiples
+// of four floats) and slides the K taps of that row over them, so one LDS row read feeds 8 K FMAs.  The taps and the radius are uniform
+// over the workgroup and come through the scalar data path; the body is instantiated per radius and chosen by a uniform switch, so the
+// loops run to the sample's own r with every register index static.  No atomics, no scratch.
+constexpr int F2D_TH = FSR_FILTER2D_TILE_H, F2D_TW = FSR_FILTER2D_TILE_W, F2D_RUN = 8;
+constexpr int F2D_PITCH = F2D_TW + 2 * FSR_FILTER2D_MAX_RADIUS;                      // 84 floats = 21 x 16 bytes
+static_assert(F2D_TH * (F2D_TW / F2D_RUN) == 256 && F2D_PITCH % 4 == 0 && F2D_PITCH <= 128, "filter2d_kernel's thread layout");
+
+template <int R>
+__device__ __forceinline__ void filter2d_rows(const float* tile, const float* __restrict__ taps, int ly, int x0, float (&acc)[F2D_RUN]) {
+  constexpr int K = 2 * R + 1, NV = (F2D_RUN + 2 * R + 3) / 4;                       // x0 + 4 NV <= F2D_PITCH: the last read stays in its row
+#pragma unroll 1
+  for (int dy = 0; dy < K; ++dy) {
+    const float4* row = (const float4*)(tile + (ly + dy) * F2D_PITCH + x0);
+    float win[4 * NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const float4 v = row[j];
+      win[4 * j] = v.x;
+      win[4 * j + 1] = v.y;
+      win[4 * j + 2] = v.z;
+      win[4 * j + 3] = v.w;
+    }
+    const float* tr = taps + dy * K;
+#pragma unroll
+    for (int dx = 0; dx < K; ++dx) {
+      const float tv = tr[dx];
+#pragma unroll
+      for (int i = 0; i < F2D_RUN; ++i) acc[i] += tv * win[dx + i];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void filter2d_kernel(const float* __restrict__ in, float* __restrict__ out, int h, int w, int tiles_x,
+                                                       int tiles_y, const float* __restrict__ taps, const int* __restrict__ radii, int vec) {
+  __shared__ __attribute__((aligned(16))) float tile[(F2D_TH + 2 * FSR_FILTER2D_MAX_RADIUS) * F2D_PITCH];
+  const int t = threadIdx.x;
+  int b = blockIdx.x;
+  const int X0 = (b % tiles_x) * F2D_TW;
+  b /= tiles_x;
+  const int Y0 = (b % tiles_y) * F2D_TH;
+  const int nc = b / tiles_y;                                                        // 3 n + c
+  const int n = nc / 3;
+  int r = radii[n];                                                                  // uniform over the workgroup
+  r = r < 0 ? 0 : (r > FSR_FILTER2D_MAX_RADIUS ? FSR_FILTER2D_MAX_RADIUS : r);
+  const size_t plane = (size_t)h * w;
+  const float* src = in + (size_t)nc * plane;
+  const int ly = t >> 3, x0 = (t & 7) * F2D_RUN;
+  const int y = Y0 + ly, x = X0 + x0;
+  float* dst = out + (size_t)nc * plane + (size_t)y * w + x;
+  if (r == 0) {                                                                      // a copy, bit for bit
+    if (y < h) {
+      const float* s = src + (size_t)y * w + x;
+#pragma unroll
+      for (int i = 0; i < F2D_RUN; ++i)
+        if (x + i < w) dst[i] = s[i];
+    }
+    return;
+  }
+  const int rows = (h - Y0 < F2D_TH ? h - Y0 : F2D_TH) + 2 * r, cols = (w - X0 < F2D_TW ? w - X0 : F2D_TW) + 2 * r;
+  const int lx = t & 127;
+  if (lx < cols) {
+    int xs = X0 + lx - r;
+    xs = xs < 0 ? 0 : (xs > w - 1 ? w - 1 : xs);
+    for (int yy = t >> 7; yy < rows; yy += 2) {
+      int ys = Y0 + yy - r;
+      ys = ys < 0 ? 0 : (ys > h - 1 ? h - 1 : ys);
+      tile[yy * F2D_PITCH + lx] = src[(size_t)ys * w + xs];
+    }
+  }
+  __syncthreads();
+  float acc[F2D_RUN];
+#pragma unroll
+  for (int i = 0; i < F2D_RUN; ++i) acc[i] = 0.f;
+  const float* tp = taps + (size_t)n * FSR_FILTER2D_TAPS;
+  switch (r) {
+    case 1: filter2d_rows<1>(tile, tp, ly, x0, acc); break;
+    case 2: filter2d_rows<2>(tile, tp, ly, x0, acc); break;
+    case 3: filter2d_rows<3>(tile, tp, ly, x0, acc); break;
+    case 4: filter2d_rows<4>(tile, tp, ly, x0, acc); break;
+    case 5: filter2d_rows<5>(tile, tp, ly, x0, acc); break;
+    case 6: filter2d_rows<6>(tile, tp, ly, x0, acc); break;
+    case 7: filter2d_rows<7>(tile, tp, ly, x0, acc); break;
+    case 8: filter2d_rows<8>(tile, tp, ly, x0, acc); break;
+    case 9: filter2d_rows<9>(tile, tp, ly, x0, acc); break;
+    default: filter2d_rows<10>(tile, tp, ly, x0, acc); break;
+  }
+  if (y >= h) return;
+  if (vec && x + F2D_RUN <= w) {                                                     // w % 4 == 0 and a 16-byte aligned batch (host checked)
+    ((float4*)dst)[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    ((float4*)dst)[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < F2D_RUN; ++i)
+    if (x + i < w) dst[i] = acc[i];
+}
+
+// ------------------------------------------------------------------------------------------ resize with a table per sample
+__device__ __forceinline__ int table_index(const int* sel, int n, int nf) {
+  const int f = sel[n];
+  return f < 0 ? 0 : (f > nf - 1 ? nf - 1 : f);
+}
+
+// pass 1: tmp[n][c][y][xo] = sum_k wx[f][xo][k] * in[n][c][y][xmin[f][xo] + k], f = sel[n]
+__global__ __launch_bounds__(256) void resize_select_hpass_kernel(const float* __restrict__ in, float* __restrict__ tmp, int ih, int iw, int ow,
+                                                                  const float* __restrict__ wx, const int* __restrict__ xmin,
+                                                                  const int* __restrict__ xsize, int kx, int nf, const int* __restrict__ sel,
+                                                                  long long total) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int xo = (int)(i % ow);
+  const long long row = i / ow;                                     // (n 3 + c) ih + y
+  const int n = (int)(row / (3LL * ih));
+  const int f = table_index(sel, n, nf);
+  const float* wt = wx + ((size_t)f * ow + xo) * kx;
+  const int x0 = xmin[f * ow + xo], ks = xsize[f * ow + xo];
+  const float* src = in + (size_t)row * iw + x0;
+  float s = 0.f;
+  for (int k = 0; k < ks; ++k) s += wt[k] * src[k];
+  tmp[i] = s;
+}
+
+// pass 2: out[n][c][yo][xo] = sum_k wy[f][yo][k] * tmp[n][c][ymin[f][yo] + k][xo]
+__global__ __launch_bounds__(256) void resize_select_vpass_kernel(const float* __restrict__ tmp, float* __restrict__ out, int ih, int oh, int ow,
+                                                                  const float* __restrict__ wy, const int* __restrict__ ymin,
+                                                                  const int* __restrict__ ysize, int ky, int nf, const int* __restrict__ sel,
+                                                                  long long total) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int xo = (int)(i % ow);
+  const int yo = (int)((i / ow) % oh);
+  const long long nc = i / ((long long)ow * oh);
+  const int f = table_index(sel, (int)(nc / 3), nf);
+  const float* wt = wy + ((size_t)f * oh + yo) * ky;
+  const int y0 = ymin[f * oh + yo], ks = ysize[f * oh + yo];
+  const float* col = tmp + ((size_t)nc * ih + y0) * ow + xo;
+  float s = 0.f;
+  for (int k = 0; k < ks; ++k) s += wt[k] * col[(size_t)k * ow];
+  out[i] = s;
+}
+
 int batch_check(const char* who, int n, int h, int w) {
   if (n <= 0 || h <= 0 || w <= 0) return fsr_fail(-2, "%s: n, h and w must be positive (n = %d, h = %d, w = %d)", who, n, h, w);
   if (3LL * h * w >= 0x80000000LL) return fsr_fail(-2, "%s: a sample of 3 x %d x %d elements does not fit in 31 bits", who, h, w);
@@ -260,7 +419,7 @@ extern "C" int fsr_degrade_blur_noise(const float* in, float* out, float* tmp, i
   const unsigned blocks = stride_blocks(total);
   if (!blur) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(blur_vpass_noise_kernel<false, true>), dim3(blocks), dim3(256), 0, stream, in, out, h, w, taps, radii,
-                       noise_sigma, seeds, total);
+                       noise_sigma, seeds, (const int*)nullptr, total);
     fsr_note_kernel("noise_kernel");
     return fsr_check_launch("noise_kernel");
   }
@@ -268,12 +427,61 @@ extern "C" int fsr_degrade_blur_noise(const float* in, float* out, float* tmp, i
   if (int rc = fsr_check_launch("blur_hpass_kernel")) return rc;
   if (noise)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(blur_vpass_noise_kernel<true, true>), dim3(blocks), dim3(256), 0, stream, (const float*)tmp, out, h, w,
-                       taps, radii, noise_sigma, seeds, total);
+                       taps, radii, noise_sigma, seeds, (const int*)nullptr, total);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(blur_vpass_noise_kernel<true, false>), dim3(blocks), dim3(256), 0, stream, (const float*)tmp, out, h, w,
-                       taps, radii, noise_sigma, seeds, total);
+                       taps, radii, noise_sigma, seeds, (const int*)nullptr, total);
   fsr_note_kernel(noise ? "blur_hpass_kernel+blur_vpass_noise_kernel" : "blur_hpass_kernel+blur_vpass_kernel");
   return fsr_check_launch("blur_vpass_noise_kernel");
+}
+
+extern "C" int fsr_filter2d(const float* in, float* out, int n, int h, int w, const float* taps, const int* radii, fsr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!in || !out || !taps || !radii) return fsr_fail(-1, "fsr_filter2d: null argument");
+  if (in == out) return fsr_fail(-2, "fsr_filter2d: the output must not be the input (a workgroup reads its neighbours' pixels)");
+  if (int rc = batch_check("fsr_filter2d", n, h, w)) return rc;
+  const int tiles_x = (w + F2D_TW - 1) / F2D_TW, tiles_y = (h + F2D_TH - 1) / F2D_TH;
+  const long long blocks = 3LL * n * tiles_x * tiles_y;
+  if (blocks > 0x7fffffffLL) return fsr_fail(-2, "fsr_filter2d: %lld workgroups do not fit in one launch", blocks);
+  const int vec = (w % 4 == 0) && ((uintptr_t)out % 16 == 0);
+  hipLaunchKernelGGL(filter2d_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, out, h, w, tiles_x, tiles_y, taps, radii, vec);
+  fsr_note_kernel("filter2d_kernel");
+  return fsr_check_launch("filter2d_kernel");
+}
+
+extern "C" int fsr_degrade_noise_kinds(const float* in, float* out, int n, int h, int w, const float* strength, const int* flags,
+                                       const unsigned* seeds, fsr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!in || !out || !strength || !flags || !seeds) return fsr_fail(-1, "fsr_degrade_noise_kinds: null argument");
+  if (int rc = batch_check("fsr_degrade_noise_kinds", n, h, w)) return rc;
+  const long long total = 3LL * h * w * n;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(blur_vpass_noise_kernel<false, true, true>), dim3(stride_blocks(total)), dim3(256), 0, stream, in, out, h, w,
+                     (const float*)nullptr, (const int*)nullptr, strength, seeds, flags, total);
+  fsr_note_kernel("noise_kinds_kernel");
+  return fsr_check_launch("noise_kinds_kernel");
+}
+
+extern "C" int fsr_resize_select(const float* in, float* out, float* tmp, int n, int ih, int iw, int oh, int ow, const float* wx, const int* xmin,
+                                 const int* xsize, int kx, const float* wy, const int* ymin, const int* ysize, int ky, int nf, const int* sel,
+                                 fsr_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!in || !out || !tmp || !wx || !xmin || !xsize || !wy || !ymin || !ysize || !sel) return fsr_fail(-1, "fsr_resize_select: null argument");
+  if (tmp == in || tmp == out || in == out) return fsr_fail(-2, "fsr_resize_select: in, tmp and out must be three buffers");
+  if (int rc = batch_check("fsr_resize_select", n, ih, iw)) return rc;
+  if (oh <= 0 || ow <= 0 || kx <= 0 || ky <= 0 || nf <= 0)
+    return fsr_fail(-2, "fsr_resize_select: oh, ow, kx, ky and nf must be positive (got %d, %d, %d, %d, %d)", oh, ow, kx, ky, nf);
+  if (3LL * ih * ow >= 0x80000000LL) return fsr_fail(-2, "fsr_resize_select: an intermediate sample of 3 x %d x %d elements does not fit in 31 bits", ih, ow);
+  if (3LL * oh * ow >= 0x80000000LL) return fsr_fail(-2, "fsr_resize_select: an output sample of 3 x %d x %d elements does not fit in 31 bits", oh, ow);
+  const long long total1 = 3LL * n * ih * ow, total2 = 3LL * n * oh * ow;
+  const long long blocks1 = (total1 + 255) / 256, blocks2 = (total2 + 255) / 256;
+  if (blocks1 > 0x7fffffffLL || blocks2 > 0x7fffffffLL) return fsr_fail(-2, "fsr_resize_select: %lld workgroups do not fit in one launch", blocks1 > blocks2 ? blocks1 : blocks2);
+  hipLaunchKernelGGL(resize_select_hpass_kernel, dim3((unsigned)blocks1), dim3(256), 0, stream, in, tmp, ih, iw, ow, wx, xmin, xsize, kx, nf, sel,
+                     total1);
+  if (int rc = fsr_check_launch("resize_select_hpass_kernel")) return rc;
+  hipLaunchKernelGGL(resize_select_vpass_kernel, dim3((unsigned)blocks2), dim3(256), 0, stream, (const float*)tmp, out, ih, oh, ow, wy, ymin,
+                     ysize, ky, nf, sel, total2);
+  fsr_note_kernel("resize_select_hpass_kernel+resize_select_vpass_kernel");
+  return fsr_check_launch("resize_select_vpass_kernel");
 }
 
 extern "C" int fsr_jpeg_roundtrip(const float* in, float* out, int n, int h, int w, const int* quality, int subsampling, fsr_stream_t stream_) {

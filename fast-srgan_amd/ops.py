@@ -1653,6 +1653,19 @@ def jpeg_roundtrip_dev(x, dev_words, subsampling="420"):
     return out
 
 
+def jpeg_quality_dev(x, dev_quality, subsampling="420"):
+    """fsr_jpeg_roundtrip with a block of its own for the qualities (int32 [N] on the device): the second round's JPEG."""
+    _check_degrade_input(x, "jpeg_roundtrip")
+    if subsampling not in JPEG_SUBSAMPLINGS:
+        raise ValueError("jpeg_roundtrip: subsampling must be one of %s, got %r" % (JPEG_SUBSAMPLINGS, subsampling))
+    n, _, h, w = x.shape
+    if dev_quality.dtype != torch.int32 or dev_quality.numel() != n or dev_quality.device != x.device or not dev_quality.is_contiguous():
+        raise ValueError("jpeg_roundtrip: dev_quality must hold %d contiguous int32 words on %s" % (n, x.device))
+    out = torch.empty_like(x)
+    L.check(L.lib().fsr_jpeg_roundtrip(_p(x), _p(out), n, h, w, dev_quality.data_ptr(), chroma_code(subsampling), _stream()), "fsr_jpeg_roundtrip")
+    return out
+
+
 def degrade_blur_noise(x, blur_sigma, noise_sigma, seeds):
     """Gaussian blur, then additive Gaussian noise, on a float32 (N,3,H,W) batch in [-1,1].  Per sample (sequences or
     tensors of length N): blur_sigma in LR pixels, 0 < sigma <= 3; noise_sigma in 8-bit code units, 0 < sigma <= 25; seeds, one (s0, s1)
@@ -1668,3 +1681,155 @@ def jpeg_roundtrip(x, quality, subsampling="420"):
     per-sample integer quality 1..100 (libjpeg's table scaling; 0 copies the sample), subsampling "420" or "444".  No autograd."""
     _check_degrade_input(x, "jpeg_roundtrip")
     return jpeg_roundtrip_dev(x, upload_words(degrade_words(x.shape[0], quality=quality), x.device), subsampling)
+
+
+# ------------------------------------------------------------------ per-sample 2-D filter (csrc/degrade.hip, DESIGN.md §6l)
+FILTER2D_WORDS = L.FILTER2D_TAPS + 1     # 4-byte words per sample: the K x K taps (packed, row-major) and the radius
+
+
+def filter2d_words(n, kernels):
+    """The per-sample parameters of fsr_filter2d as ONE int32 array of FILTER2D_WORDS * n words for a single host-to-device copy:
+    [taps: 441 n float32][radii: n int32].  `kernels`: n entries, each a square 2-D array of odd size K <= 21 (cast to float32 as it
+    is: dataloader.kernel_bank normalises in float64) or None for "off" (radius 0: the sample is copied)."""
+    T = L.FILTER2D_TAPS
+    kernels = _per_sample(kernels, n, "kernels")
+    words = np.zeros(FILTER2D_WORDS * n, dtype=np.int32)
+    taps = words[:T * n].view(np.float32).reshape(n, T)
+    for i, k in enumerate(kernels):
+        if k is None:
+            continue
+        k = np.asarray(k)
+        if k.ndim != 2 or k.shape[0] != k.shape[1] or k.shape[0] % 2 != 1 or k.shape[0] > 2 * L.FILTER2D_MAX_RADIUS + 1:
+            raise ValueError("filter2d: kernel %d must be square with an odd size of at most %d, got shape %s"
+                             % (i, 2 * L.FILTER2D_MAX_RADIUS + 1, k.shape))
+        if not np.isfinite(k).all():
+            raise ValueError("filter2d: kernel %d holds a value that is not finite" % i)
+        taps[i, :k.size] = k.reshape(-1)
+        words[T * n + i] = k.shape[0] // 2
+    return words
+
+
+def filter2d_dev(x, dev_words):
+    """fsr_filter2d with the parameters already on the device (`dev_words`: filter2d_words(...) uploaded, or a view of a larger block).
+    One launch whatever the radii are; a sample of radius 0 leaves it as a copy."""
+    _check_degrade_input(x, "filter2d")
+    n, _, h, w = x.shape
+    if dev_words.dtype != torch.int32 or dev_words.numel() != FILTER2D_WORDS * n or dev_words.device != x.device or not dev_words.is_contiguous():
+        raise ValueError("filter2d: dev_words must hold %d contiguous int32 words on %s" % (FILTER2D_WORDS * n, x.device))
+    base = dev_words.data_ptr()
+    out = torch.empty_like(x)
+    L.check(L.lib().fsr_filter2d(_p(x), _p(out), n, h, w, base, base + 4 * L.FILTER2D_TAPS * n, _stream()), "fsr_filter2d")
+    return out
+
+
+def filter2d(x, kernels):
+    """A K x K filter per sample on a float32 (N,3,H,W) batch: out[n,c,y,x] = sum_dy sum_dx k_n[dy + r, dx + r] *
+    in[n, c, clamp(y + dy), clamp(x + dx)] -- correlation, clamped borders, float32 accumulation, dy outer and dx inner.  `kernels`: one
+    square array of odd size K <= 21 per sample, or None to copy that sample.  No autograd."""
+    _check_degrade_input(x, "filter2d")
+    return filter2d_dev(x, upload_words(filter2d_words(x.shape[0], kernels), x.device))
+
+
+# ------------------------------------------------------------------ resize with a tap table per sample (csrc/degrade.hip, DESIGN.md §6l)
+class ResizeTables:
+    """F tap tables per axis for fsr_resize_select, on the device: `x_tables` / `y_tables` are lists of (xmin, xsize, w, kmax) in the
+    layout of dataloader.aa_bicubic_taps (one entry per filter, every table of an axis for the same output size); the rows are padded
+    to the widest kmax.  Checked here, since the C entry point only sees pointers: xmin >= 0, 1 <= xsize <= kmax, xmin + xsize <= the
+    input size."""
+
+    def __init__(self, x_tables, y_tables, in_h, in_w, device):
+        if len(x_tables) != len(y_tables) or not x_tables:
+            raise ValueError("ResizeTables: one table per filter and axis, at least one filter")
+        self.nf, self.in_h, self.in_w = len(x_tables), int(in_h), int(in_w)
+        self.x, self.out_w, self.kx = self._pack(x_tables, self.in_w, device)
+        self.y, self.out_h, self.ky = self._pack(y_tables, self.in_h, device)
+
+    @staticmethod
+    def _pack(tables, in_size, device):
+        out = len(tables[0][0])
+        kmax = max(int(t[3]) for t in tables)
+        w = np.zeros((len(tables), out, kmax), dtype=np.float32)
+        lo = np.zeros((len(tables), out), dtype=np.int32)
+        sz = np.zeros((len(tables), out), dtype=np.int32)
+        for f, (xmin, xsize, wt, k) in enumerate(tables):
+            xmin, xsize, wt = np.asarray(xmin), np.asarray(xsize), np.asarray(wt, dtype=np.float32)
+            if xmin.shape != (out,) or xsize.shape != (out,) or wt.shape != (out, int(k)):
+                raise ValueError("ResizeTables: table %d does not have the layout of aa_bicubic_taps for %d outputs" % (f, out))
+            if xmin.min() < 0 or xsize.min() < 1 or xsize.max() > k or (xmin + xsize).max() > in_size:
+                raise ValueError("ResizeTables: table %d reads outside its %d input samples or its %d tap slots" % (f, in_size, k))
+            w[f, :, :int(k)], lo[f], sz[f] = wt, xmin, xsize
+        dev = tuple(torch.from_numpy(a).to(device) for a in (w, lo, sz))
+        return dev, out, kmax
+
+
+def resize_select_dev(x, tables, dev_sel):
+    """fsr_resize_select with the table indices already on the device (int32 [N]): horizontal pass, then vertical pass."""
+    _check_degrade_input(x, "resize_select")
+    n, _, h, w = x.shape
+    if (h, w) != (tables.in_h, tables.in_w) or tables.x[0].device != x.device:
+        raise ValueError("resize_select: the tables were built for %dx%d inputs on %s, got %dx%d on %s"
+                         % (tables.in_h, tables.in_w, tables.x[0].device, h, w, x.device))
+    if dev_sel.dtype != torch.int32 or dev_sel.numel() != n or dev_sel.device != x.device or not dev_sel.is_contiguous():
+        raise ValueError("resize_select: dev_sel must hold %d contiguous int32 table indices on %s" % (n, x.device))
+    out = torch.empty((n, 3, tables.out_h, tables.out_w), dtype=torch.float32, device=x.device)
+    tmp = torch.empty((n, 3, h, tables.out_w), dtype=torch.float32, device=x.device)
+    (wx, xmin, xsize), (wy, ymin, ysize) = tables.x, tables.y
+    L.check(L.lib().fsr_resize_select(_p(x), _p(out), _p(tmp), n, h, w, tables.out_h, tables.out_w, _p(wx), _p(xmin), _p(xsize), tables.kx,
+                                      _p(wy), _p(ymin), _p(ysize), tables.ky, tables.nf, dev_sel.data_ptr(), _stream()), "fsr_resize_select")
+    return out
+
+
+def resize_select(x, tables, sel):
+    """Resizes a float32 (N,3,H,W) batch with tap table sel[i] of `tables` (a ResizeTables) for sample i: separable, horizontal pass
+    first, float32 accumulation in tap order.  An index outside 0 .. tables.nf - 1 is refused.  No autograd."""
+    sel = [int(v) for v in _per_sample(sel, x.shape[0], "sel")]
+    if any(not 0 <= v < tables.nf for v in sel):
+        raise ValueError("resize_select: table indices must lie in 0..%d, got %r" % (tables.nf - 1, sel))
+    return resize_select_dev(x, tables, upload_words(np.asarray(sel, dtype=np.int32), x.device))
+
+
+# ------------------------------------------------------------------ noise kinds (csrc/degrade.hip, DESIGN.md §6l)
+SHOT_GAIN_MAX = 3.0
+NOISE_KIND_WORDS = 4       # 4-byte words per sample: the strength, the flags, two seed words
+
+
+def noise_kind_words(n, strength, flags, seeds):
+    """The per-sample parameters of fsr_degrade_noise_kinds as ONE int32 array: [strength: n float32][flags: n int32][seeds: 2 n uint32].
+    strength: the sigma in code units (0..25) of a Gaussian sample, the gain g (0..3) of a shot sample (flag L.NOISE_SHOT); 0 = off."""
+    st = [float(s) for s in _per_sample(strength, n, "strength")]
+    fl = [int(f) for f in _per_sample(flags, n, "flags")]
+    if any(f & ~(L.NOISE_SHOT | L.NOISE_GREY) for f in fl):
+        raise ValueError("noise flags are bits of NOISE_SHOT | NOISE_GREY, got %r" % (fl,))
+    for s, f in zip(st, fl):
+        top = SHOT_GAIN_MAX if f & L.NOISE_SHOT else NOISE_SIGMA_MAX
+        if not 0.0 <= s <= top:
+            raise ValueError("noise strength must lie in [0, %g] (%s; 0 = off), got %r" % (top, "shot gain" if f & L.NOISE_SHOT else "sigma", s))
+    sd = np.array(_per_sample(seeds, n, "seeds"), dtype=np.int64).reshape(n, 2)
+    if sd.min() < 0 or sd.max() > 0xffffffff:
+        raise ValueError("seed words must be unsigned 32-bit integers")
+    words = np.zeros(NOISE_KIND_WORDS * n, dtype=np.int32)
+    words[:n].view(np.float32)[:] = st
+    words[n:2 * n] = fl
+    words[2 * n:].view(np.uint32)[:] = sd.reshape(-1).astype(np.uint32)
+    return words
+
+
+def degrade_noise_kinds_dev(x, dev_words):
+    """fsr_degrade_noise_kinds with noise_kind_words(...) already on the device: one launch."""
+    _check_degrade_input(x, "degrade_noise_kinds")
+    n, _, h, w = x.shape
+    if dev_words.dtype != torch.int32 or dev_words.numel() != NOISE_KIND_WORDS * n or dev_words.device != x.device or not dev_words.is_contiguous():
+        raise ValueError("degrade_noise_kinds: dev_words must hold %d contiguous int32 words on %s" % (NOISE_KIND_WORDS * n, x.device))
+    base = dev_words.data_ptr()
+    out = torch.empty_like(x)
+    L.check(L.lib().fsr_degrade_noise_kinds(_p(x), _p(out), n, h, w, base, base + 4 * n, base + 8 * n, _stream()), "fsr_degrade_noise_kinds")
+    return out
+
+
+def degrade_noise_kinds(x, strength, flags, seeds):
+    """Additive noise of a kind per sample on a float32 (N,3,H,W) batch in [-1,1].  flags[i] = 0: Gaussian colour
+    noise of sigma strength[i] code units, what degrade_blur_noise adds; L.NOISE_SHOT: shot noise in its normal approximation,
+    x += z sqrt(g v) 2/255 with v the element's code and g = strength[i]; L.NOISE_GREY (may be combined): one z per pixel, shared by its
+    three channels.  strength 0 copies the sample.  No autograd."""
+    _check_degrade_input(x, "degrade_noise_kinds")
+    return degrade_noise_kinds_dev(x, upload_words(noise_kind_words(x.shape[0], strength, flags, seeds), x.device))

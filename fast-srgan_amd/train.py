@@ -14,7 +14,7 @@ import torch
 
 from . import distributed as D
 from .config import enter_run_dir, hydra_run_settings, load_config
-from .dataloader import Augmentation, Degradation, DeviceBatchLoader, NumpyImagesDataset
+from .dataloader import SECOND_KEYS, Augmentation, Degradation, DeviceBatchLoader, NumpyImagesDataset
 from .trainer import Trainer
 
 
@@ -58,17 +58,29 @@ def write_images_to_numpy_arrays(image_list, output_dir, threads=16):
             list(executor.map(lambda t: _write(*t), todo))
 
 
+# data.degradation.* keys of the high-order model; `second` is a group of SECOND_KEYS
+HIGH_ORDER_KEYS = ("kernel_prob", "kernel_size", "kernel_kinds", "kernel_sigma", "kernel_beta_generalized", "kernel_beta_plateau", "sinc_prob",
+                   "resize_filters", "noise_shot_prob", "noise_shot_gain", "noise_grey_prob", "second", "final_sinc_prob", "final_sinc_size")
+
+
 def make_degradation(config, seed_value):
     """The Degradation of one loader from data.degradation.* (every key optional, everything off by default); None when every
     probability is 0, so that such a run builds the loaders it always built."""
     node = getattr(config.data, "degradation", None)
-    keys = ("blur_sigma", "blur_prob", "noise_sigma", "noise_prob", "jpeg_quality", "jpeg_prob", "jpeg_subsampling")
+    keys = ("blur_sigma", "blur_prob", "noise_sigma", "noise_prob", "jpeg_quality", "jpeg_prob", "jpeg_subsampling") + HIGH_ORDER_KEYS
     given = {} if node is None else {k: v for k, v in vars(node).items() if v is not None}
     unknown = sorted(set(given) - set(keys))
     if unknown:
         raise ValueError("unknown data.degradation key(s) %s (known: %s)" % (unknown, ", ".join(keys)))
     if "jpeg_subsampling" in given:
         given["jpeg_subsampling"] = str(given["jpeg_subsampling"])          # YAML reads 420 as an integer
+    if "second" in given:                                                    # data.degradation.second.*: the second round's own group
+        if not hasattr(given["second"], "__dict__"):
+            raise ValueError("data.degradation.second is a group of keys (%s), got %r" % (", ".join(SECOND_KEYS), given["second"]))
+        given["second"] = {k: v for k, v in vars(given["second"]).items() if v is not None}
+        unknown = sorted(set(given["second"]) - set(SECOND_KEYS))
+        if unknown:
+            raise ValueError("unknown data.degradation.second key(s) %s (known: %s)" % (unknown, ", ".join(SECOND_KEYS)))
     deg = Degradation(seed=seed_value, **given)
     return deg if deg.enabled else None
 

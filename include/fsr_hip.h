@@ -548,6 +548,44 @@ int fsr_degrade_blur_noise(const float* in, float* out, float* tmp, int n, int h
                            const float* noise_sigma, const unsigned* seeds, fsr_stream_t stream);
 int fsr_jpeg_roundtrip(const float* in, float* out, int n, int h, int w, const int* quality, int subsampling, fsr_stream_t stream);
 
+/* ------------------------------------------------------------------ per-sample 2-D filter (added within ABI 16: a new entry point only)
+ * fsr_filter2d: a non-separable K x K filter per sample on a float NCHW batch [n,3,h,w], K = 2 r + 1 <= 21: the blur of a kernel bank
+ * (rotated / generalised / plateau Gaussians, sinc) in front of a sampler.  One launch:
+ *   out[i][c][y][x] = sum_{dy = -r..r} sum_{dx = -r..r} taps[i][(dy + r) K + dx + r] * in[i][c][clamp(y + dy)][clamp(x + dx)]
+ * -- correlation, not convolution; the source index is clamped at the borders; float accumulation from 0 in the order dy outer, dx inner.
+ * taps: DEVICE float [n][FSR_FILTER2D_TAPS], sample i's K x K taps row-major and packed at the start of its block (built and normalised
+ * on the host; the slots behind K * K are not read).  radii: DEVICE int [n], read as clamped to 0 .. FSR_FILTER2D_MAX_RADIUS;
+ * radii[i] = 0 copies the sample bit for bit through the same launch (its taps are not read).  One workgroup owns
+ * FSR_FILTER2D_TILE_H x FSR_FILTER2D_TILE_W outputs of one (sample, channel).
+ * Refused (-1 / -2, nothing launched): null pointers, n, h or w < 1, in == out, 3 h w >= 2^31. */
+#define FSR_FILTER2D_MAX_RADIUS 10
+#define FSR_FILTER2D_TAPS 441
+#define FSR_FILTER2D_TILE_H 32
+#define FSR_FILTER2D_TILE_W 64
+int fsr_filter2d(const float* in, float* out, int n, int h, int w, const float* taps, const int* radii, fsr_stream_t stream);
+
+/* fsr_resize_select: separable down-scale (or any resize) of a float NCHW batch [n,3,ih,iw] -> [n,3,oh,ow] with a tap table chosen per
+ * sample, horizontal pass in -> tmp [n,3,ih,ow], then vertical pass tmp -> out: two launches, float accumulation in tap order.
+ *   tmp[i][c][y][xo]  = sum_{k < xsize[f][xo]} wx[f][xo][k] * in[i][c][y][xmin[f][xo] + k]
+ *   out[i][c][yo][xo] = sum_{k < ysize[f][yo]} wy[f][yo][k] * tmp[i][c][ymin[f][yo] + k][xo]            f = sel[i]
+ * wx float [nf][ow][kx], xmin / xsize int [nf][ow] and wy float [nf][oh][ky], ymin / ysize int [nf][oh]: nf normalised tables per axis in
+ * the layout of fsr_crop_resize's (the caller keeps xmin + xsize <= iw, xsize <= kx and likewise for y); sel: int [n], read as clamped
+ * to 0 .. nf - 1.  Every array is a DEVICE pointer.  No [-1,1] mapping: float in, float out.
+ * Refused (-1 / -2, nothing launched): null pointers, extents, nf, kx or ky < 1, tmp == in or out, in == out, 3 ih iw >= 2^31. */
+int fsr_resize_select(const float* in, float* out, float* tmp, int n, int ih, int iw, int oh, int ow, const float* wx, const int* xmin,
+                      const int* xsize, int kx, const float* wy, const int* ymin, const int* ysize, int ky, int nf, const int* sel,
+                      fsr_stream_t stream);
+
+/* fsr_degrade_noise_kinds: fsr_degrade_blur_noise's noise-only form with a kind per sample.  strength: float [n], flags: int [n] of
+ * FSR_NOISE_SHOT | FSR_NOISE_GREY, seeds as there.  Without FSR_NOISE_SHOT strength is the sigma of fsr_degrade_blur_noise and the
+ * result is that call's, bit for bit.  FSR_NOISE_SHOT: strength is a gain g in code units and
+ *   x += z * sqrtf(g * v) * (2 / 255),   v = clamp((x + 1) * 127.5, 0, 255)
+ * -- the normal approximation of Poisson (shot) noise, not a Poisson sampler.  FSR_NOISE_GREY: the hash's element index is y w + x
+ * in place of (c h + y) w + x, so the three channels of a pixel share one z.  strength <= 0 copies the sample.  One launch. */
+enum { FSR_NOISE_SHOT = 1, FSR_NOISE_GREY = 2 };
+int fsr_degrade_noise_kinds(const float* in, float* out, int n, int h, int w, const float* strength, const int* flags, const unsigned* seeds,
+                            fsr_stream_t stream);
+
 /* ------------------------------------------------------------------ strided element-wise losses (added within ABI 16: new entry points only)
  * The pixel term of the training objective and the least-squares adversarial term.  a, b: float [n,c,h,w], each read through its OWN
  * four strides (in elements; an NCHW view of an NHWC buffer, a planar batch, a slice) -- nothing is copied.  With d = a - b and
